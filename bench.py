@@ -7,14 +7,21 @@ all-reduce of the 5060-float student gradient when N > 1) -- the reference's hot
 iteration (mlp_train.py:143-204) batched.  Unit: env-steps/s summed over all ranks.
 
   python bench.py [--gpus N --steps K --warmup W --workload c4|c2|c3|c5 --envs-per-gpu E]
+                  [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Default workload: BASELINE config 4's 262,144 envs on EVERY GPU
 (weak scaling: per-GPU work fixed as N grows), teacher-driven, MSE, fp32 -- the metric is
-quoted at 1/2/4/8 MI355X, which is config 4.  Rank 0 prints one JSON line, with a
-`roofline` object for the dominant kernel (rollout_kernel, timed with HIP events on its
-stream inside the timed region) and a `cpu_baseline` (the C f32 restatement, OpenMP, on a
-bounded sample; rank 0 at N = 1 only).
+quoted at 1/2/4/8 MI355X, which is config 4.  Rank 0 prints one JSON line.
+
+A plain run does only what the headline needs: set-up, clock settle, W warm-up steps, the K
+timed steps, the --dump-outputs files, the line.  --full adds every other leg to the line:
+the convergence legs (run before the timed region), a `roofline` object for the dominant
+kernel (rollout_kernel, timed with HIP events on its stream in a pass after the timed
+region), the other f32 mode, the K-step launch, the other BASELINE configs, the strong
+projection, the fixture and PPO legs and a `cpu_baseline` (the C f32 restatement, OpenMP, on
+a bounded sample; rank 0 at N = 1 only).  The --no-* / --accum / --conv-steps / --fixture-steps
+options trim --full's legs and mean nothing without it.
 """
 from __future__ import annotations
 
@@ -78,6 +85,13 @@ def parse():
     ap.add_argument("--settle-ms", type=float, default=300.0,
                     help="untimed steps for this long before the W warm-up steps, so that the GPU's "
                          "clocks have left their idle state (reported as 'settle' in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run and report every secondary leg (convergence, roofline, other "
+                         "f32 mode, K-step launch, other workloads, strong projection, fixture, PPO, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left a caller of the step -- student "
+                         "parameters, gradient, env state, the step's metrics row -- as DIR/<name>.npy (rank 0's "
+                         "shard; identical from run to run for the same arguments)")
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--envs-per-gpu", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-4)
@@ -309,6 +323,34 @@ def settle(step, dev, ms, world=1):
         step()
     torch.cuda.synchronize(dev)
     return {"steps": k, "ms": (time.perf_counter() - t0) * 1e3}
+
+
+DUMP_MAX_ENVS = 1 << 20     # env_state columns written by --dump-outputs (8 f32 each: 32 MiB at most)
+
+
+def capture_outputs(tr):
+    """--dump-outputs, first half: what the step just taken left for a caller of
+    DistillTrainer.step() -- the student's parameters after its Adam step, the step's gradient,
+    the envs' state ([8, n] SoA) and the step's metrics row -- copied on the device (plus the
+    16-byte metrics read), so that the legs that follow start without an idle gap."""
+    return {"student_params": tr.student_params(), "grad": tr.grad().clone(), "env_state": tr.env_state(),
+            "metrics": tr.metrics(1)}
+
+
+def dump_outputs(captured, path):
+    """--dump-outputs, second half: the captured arrays as float32 / float64 DIR/<name>.npy;
+    beyond DUMP_MAX_ENVS envs a fixed seeded sample of env_state's columns, their indices in
+    env_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in captured.items()}
+    n = arrays["env_state"].shape[1]
+    if n > DUMP_MAX_ENVS:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_ENVS, replace=False))
+        arrays["env_state"] = np.ascontiguousarray(arrays["env_state"][:, idx])
+        arrays["env_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
 
 
 def time_leg(wl, n, sdt, split, dev, lr, steps, warmup, npass=100, settle_ms=0.0):
@@ -857,7 +899,8 @@ def main():
             if c is None:
                 exchange[f"{kind}_us"] = f"unavailable: {why}"
                 continue
-            exchange[f"{kind}_us"] = exchange_latency(c, dev)["us"]
+            if args.full:
+                exchange[f"{kind}_us"] = exchange_latency(c, dev)["us"]
             exchange[f"{kind}_view"] = comm_view(c, dev, world)
             cands[kind] = c
         exchange["floats"] = 5060
@@ -880,19 +923,20 @@ def main():
     sdt = wl.get("student_dtype", "f32")
     split = args.f32_mode == "split"
 
-    # The convergence leg runs first, on trainers of its own: it is the north star's student
-    # action-MSE check, and its ~1,000 back-to-back steps also take the GPU out of its idle
-    # clocks, so the short timed region below (the driver runs 20 steps of ~0.12 ms) measures
-    # the kernels rather than the clock ramp.
+    # --full: the convergence leg runs first, on trainers of its own: it is the north star's
+    # student action-MSE check, and its ~1,000 back-to-back steps also take the GPU out of its
+    # idle clocks, so a short timed region below (20 steps of ~0.12 ms) measures the kernels
+    # rather than the clock ramp.  A plain run has settle() for that.
     conv = conv_small = None
-    fitted, fit_info = fitted_teacher(dev) if ((args.conv_steps > 0 and world == 1) or args.teacher == "fitted") \
+    conv_steps = args.conv_steps if args.full else 0
+    fitted, fit_info = fitted_teacher(dev) if ((conv_steps > 0 and world == 1) or args.teacher == "fitted") \
         else (None, None)
     if args.teacher == "fitted" and fitted is None:
         raise SystemExit("--teacher fitted needs tests/golden/reacher_fixture.npz")
-    ppo_t, ppo_info = ppo_teacher_info(dev) if ((args.conv_steps > 0 and world == 1) or args.teacher == "ppo") \
+    ppo_t, ppo_info = ppo_teacher_info(dev) if ((conv_steps > 0 and world == 1) or args.teacher == "ppo") \
         else (None, None)
     teacher = fitted if args.teacher == "fitted" else ppo_t if args.teacher == "ppo" else None
-    if args.conv_steps > 0:
+    if conv_steps > 0:
         conv = convergence(wl, n, sdt, dev, rank, world, args.lr, args.conv_steps, comm=comm, split=split,
                            teacher=teacher)
         # the same check at a small per-GPU batch: the env-step reading of the reference's budget
@@ -903,7 +947,7 @@ def main():
                         f32_split=split)
     tr = DistillTrainer(cfg, device=dev, rank=rank, world_size=world, comm=comm, teacher=teacher)
 
-    def one_step(ev=None):
+    def one_step(ev=None, tr=tr):
         if ev is None and (world == 1 or comm is not None):
             tr.step()     # rdd_step: rollout + reduce (+ RCCL all-reduce) + Adam, one host call
             return
@@ -919,7 +963,11 @@ def main():
             tr.allreduce_grad()
             tr.launch(tr.STAGE_APPLY)
 
-    settled = settle(one_step, dev, args.settle_ms, world)
+    # settle() fixes its step count from a timing probe, so it steps a twin of the measured
+    # trainer: the measured one takes exactly warmup + steps steps, and what its last timed
+    # step leaves (--dump-outputs) is the same from run to run
+    twin = DistillTrainer(cfg, device=dev, rank=rank, world_size=world, comm=comm, teacher=teacher)
+    settled = settle(lambda: one_step(tr=twin), dev, args.settle_ms, world)
     for _ in range(args.warmup):
         one_step()
     # the timed region: exactly `steps` steps, nothing else on the stream (no timing events)
@@ -939,23 +987,29 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    captured = None
+    if args.dump_outputs and rank == 0:   # before anything else steps the measured trainer
+        captured = capture_outputs(tr)
 
-    # rollout_kernel's launch time for the roofline: a separate pass right after the timed
-    # region, HIP events on the trainer's stream around every rollout launch (an event pair
-    # costs the stream a few us per step, so it is kept out of the timed region)
-    npass = max(20, min(args.steps, 200))
+    # --full: rollout_kernel's launch time for the roofline: a separate pass right after the
+    # timed region, HIP events on the trainer's stream around every rollout launch (an event
+    # pair costs the stream a few us per step, so it is kept out of the timed region)
+    npass = max(20, min(args.steps, 200)) if args.full else 0
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(npass)]
     for k in range(npass):
         one_step(evs[k])
     torch.cuda.synchronize(dev)
-    kern_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+    kern_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs) if evs else None
+    twin.close()
+    if captured is not None:
+        dump_outputs(captured, args.dump_outputs)
 
     replicas = tr.replicas_identical() if world > 1 else True   # SURVEY §8e checksum
     if comm is not None and hasattr(comm, "check"):
         comm.check()   # (xGMI) raise if any exchange of the run waited past its limit for a peer
 
     accum = None
-    if args.accum > 1:   # secondary line: one optimiser step (+ all-reduce) per K env-steps
+    if args.full and args.accum > 1:   # secondary line: one optimiser step (+ all-reduce) per K env-steps
         K = args.accum
         accum = {"accum_steps": K}
         # fused: one K-step launch per optimiser step (rdd_step_accum); staged: K rollout launches
@@ -998,7 +1052,7 @@ def main():
     # one GPU it is the headline run itself (c4: 262,144 envs on one GPU)
     strong = None
     total = wl.get("envs_global", wl["envs"])
-    if world > 1 and not args.no_strong and not args.envs_per_gpu:
+    if args.full and world > 1 and not args.no_strong and not args.envs_per_gpu:
         strong = strong_leg(wl, total, sdt, split, dev, args.lr, max(args.steps, 100), args.warmup, rank, world, comm,
                             settle_ms=min(args.settle_ms, 100.0))
         if args.accum > 1:   # the same fixed global batch at one optimiser step per K env steps (K-step launch)
@@ -1013,9 +1067,33 @@ def main():
         dist.all_reduce(mt)
     mse = float(mt[2] / (2 * mt[3]))
 
-    if rank == 0:
+    if rank == 0:   # the headline: everything a plain run reports
         ms = elapsed * 1e3 / args.steps
         value = n * world * args.steps / elapsed
+        out = {
+            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "settle": settled, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32" if sdt == "f32" else "bf16 student (f32 accumulate) + f32 teacher",
+            "data": "synthetic: Philox(seed 0) Reacher-v2 resets, seeded synthetic teacher (normc, fixture logstd) "
+                    "and student (2x64 MlpPolicy)",
+            "config": {"workload": args.workload, "description": wl["desc"], "envs_per_gpu": n,
+                       "envs_total": n * world, "student": f"MlpPolicy 2x64 tanh (5060 params, {sdt})",
+                       "teacher": "MlpPolicy 2x64 tanh", "loss": wl["loss"], "act_with": wl["act_with"],
+                       "optimizer": f"TF1 Adam lr {args.lr}, 1 step per env-step",
+                       "parallelism": f"dp{world}", "collective": collective, "f32_mode": args.f32_mode,
+                       "f32_arith": ("hidden-layer products (K = 64) f32-emulated on bf16 MFMA: exact 3-piece bf16 "
+                                     "operand split, six partial products, f32 accumulate; the rest exact f32"
+                                     if split else "every product on v_mfma_f32_16x16x4_f32 (exact f32)")},
+            # --full: the north star's student action-MSE after the convergence leg (< 1e-3 within
+            # its budget); the timed run's own value (warmup + steps from init) is kept beside it
+            "student_mse": conv["student_mse_final"] if conv is not None else mse,
+            "student_mse_timed_run": mse, "full": args.full, "replicas_identical": replicas,
+        }
+        if exchange is not None:
+            out["exchange"] = exchange
+        if args.dump_outputs:
+            out["dump_outputs"] = args.dump_outputs
+    if rank == 0 and args.full:   # every other leg, into the same line
         launch_s = kern_ms * 1e-3
         achieved = FLOP_PER_ENV_STEP * n / launch_s / 1e12
         peak = mixed_peak(sdt, split)
@@ -1038,24 +1116,7 @@ def main():
         other = None
         if world == 1 and not args.no_exact_leg:   # the other f32 mode, same workload, for comparison
             other = time_leg(wl, n, sdt, not split, dev, args.lr, args.steps, args.warmup, settle_ms=args.settle_ms)
-        out = {
-            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "settle": settled, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32" if sdt == "f32" else "bf16 student (f32 accumulate) + f32 teacher",
-            "data": "synthetic: Philox(seed 0) Reacher-v2 resets, seeded synthetic teacher (normc, fixture logstd) "
-                    "and student (2x64 MlpPolicy)",
-            "config": {"workload": args.workload, "description": wl["desc"], "envs_per_gpu": n,
-                       "envs_total": n * world, "student": f"MlpPolicy 2x64 tanh (5060 params, {sdt})",
-                       "teacher": "MlpPolicy 2x64 tanh", "loss": wl["loss"], "act_with": wl["act_with"],
-                       "optimizer": f"TF1 Adam lr {args.lr}, 1 step per env-step",
-                       "parallelism": f"dp{world}", "collective": collective, "f32_mode": args.f32_mode,
-                       "f32_arith": ("hidden-layer products (K = 64) f32-emulated on bf16 MFMA: exact 3-piece bf16 "
-                                     "operand split, six partial products, f32 accumulate; the rest exact f32"
-                                     if split else "every product on v_mfma_f32_16x16x4_f32 (exact f32)")},
-            # the north star's student action-MSE: after the convergence leg (< 1e-3 within its
-            # budget); the timed run's own value (220 steps from init) is kept beside it
-            "student_mse": conv["student_mse_final"] if conv is not None else mse,
-            "student_mse_timed_run": mse,
+        out.update({
             "roofline": {"kernel": "rollout_kernel", "bound": "mfma", "achieved": achieved,
                          "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                          "peak_basis": ("MFMA-time-weighted peak of the FLOP mix: f32 MFMA 157.3 TF; split-emulated "
@@ -1071,16 +1132,13 @@ def main():
                                           "the timed region",
                          "hbm_gbs_algorithmic": BYTES_PER_ENV_STEP * n / launch_s / 1e9,
                          "hbm_peak_gbs": PEAK_HBM_GBS, "hbm_copy_gbs_measured": copy_gbs},
-            "replicas_identical": replicas,
-        }
+        })
         if issue is not None:
             out["roofline_issue"] = issue
         if other is not None:
             out["other_f32_mode"] = other
         if strong is not None:
             out["strong_scaling"] = strong
-        if exchange is not None:
-            out["exchange"] = exchange
         if accum is not None:
             out["accum"] = accum
         if conv is not None:
@@ -1158,6 +1216,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds, args.cpu_threads, n)
             out["cpu_baseline"]["ref_loop"] = cpu_ref_loop(min(4.0, args.cpu_seconds))
             out["cpu_baseline"]["batched_env"] = cpu_batched_env(min(4.0, args.cpu_seconds))
+    if rank == 0:
         # at N > 1 a communication library may have written to stdout without a newline
         # (gloo's "[Gloo] Rank 0 is connected ..."): start the JSON line on a line of its own
         sys.stdout.flush()

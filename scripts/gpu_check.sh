@@ -15,7 +15,7 @@ ok_or_stop() {  # $1 = exit code, $2 = step; test failures (1) continue, faults 
 }
 timeout -k 10 900 python -u -m pytest tests -m gpu -q -x -p no:cacheprovider --timeout 120 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1
 rc=$?; tail -5 "$OUT/pytest_gpu.log"; ok_or_stop $rc pytest
-timeout -k 10 420 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"; [ $rc -eq 0 ] || { echo "bench exit $rc"; exit $rc; }
 timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
   python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --accum 0 --conv-steps 0 "$@" > "$OUT/prof_bench.json" 2> "$OUT/prof.err"

@@ -2,11 +2,9 @@
 reference fixture's 25 episodes (tests/golden/reacher_fixture.npz), split over three pages
 written out of index order; the expected values repeat the reference's arithmetic (per-episode
 Python float sums in record order, averages per 5 episodes, / EPISODE_STEPS)."""
-import os
 import shutil
 
 import numpy as np
-import pytest
 
 from reacherdistilation_amd import extract_reward as er
 from reacherdistilation_amd import pages
@@ -56,9 +54,8 @@ def test_device_returns_match_the_page_returns(golden, tmp_path):
     np.testing.assert_allclose(er.device_returns(ds).numpy(), er.ExtractReward.get_return(str(tmp_path)), rtol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PAGE), reason="reference checkout not present (GPU box)")
 def test_the_reference_page_itself(golden, tmp_path):
-    shutil.copy(REF_PAGE, tmp_path / "dataset_0.json")   # test-time copy of the fixture data, not committed
+    shutil.copy(REF_PAGE, tmp_path / "dataset_0.json")   # the page under the name a PageStore looks for
     ret, _, rew = _expected(golden, 5)
     assert er.ExtractReward.get_return(str(tmp_path)) == ret
     assert er.ExtractReward.get_avg_reward(str(tmp_path), 5) == rew

@@ -2,11 +2,11 @@
 JSON written by json_tricks, reference dataset.py:31-35) and the DatasetStore paging
 semantics (dataset.py:14-65).
 
-The reference's own page (its test fixture src/distilation/tests/data/dataset.json) is not
-copied into this repo: a page in the same layout (keys s, with, rew (scalar), prev, ob, t)
-is rebuilt from the committed golden arrays (tests/golden/reacher_fixture.npz, derived from
-that fixture by tests/golden/make_golden.py), and where /root/reference exists (this build
-container, never the GPU box) the reference file itself is parsed too.
+The reference's own page (its test fixture src/distilation/tests/data/dataset.json, data
+only) is stored as tests/golden/reference_dataset.json and parsed as it is; a page in the same
+layout (keys s, with, rew (scalar), prev, ob, t) is also rebuilt from the committed golden
+arrays (tests/golden/reacher_fixture.npz, derived from that fixture by
+tests/golden/make_golden.py).
 """
 import gzip
 import json
@@ -21,7 +21,7 @@ from reacherdistilation_amd.config import MAX_CAPACITY
 from reacherdistilation_amd.dataset import DeviceDataset
 from tests.conftest import GOLDEN
 
-REF_PAGE = "/root/reference/src/distilation/tests/data/dataset.json"
+REF_PAGE = os.path.join(GOLDEN, "reference_dataset.json")
 
 
 def _fixture_layout_page(golden, path):
@@ -42,7 +42,6 @@ def page(golden, tmp_path):
     return _fixture_layout_page(golden, tmp_path / "fixture_layout.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PAGE), reason="reference checkout not present (GPU box)")
 def test_the_reference_page_itself_parses_to_the_golden_records(golden):
     rec = pages.episodes_to_records(pages.read_page(REF_PAGE))
     np.testing.assert_array_equal(rec[..., pages.F_OB:pages.F_REW], golden["ob"])
