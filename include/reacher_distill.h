@@ -180,6 +180,43 @@ int rdd_allreduce_grad(rdd_trainer* tr);
  * obs [n][11] -> t_pdflat, s_pdflat [n][4] (either output may be NULL). */
 int rdd_forward(rdd_trainer* tr, const float* obs, int64_t n, float* t_pdflat, float* s_pdflat);
 
+/* Whole-episode evaluation in one launch: n_envs evaluation envs (their own states, kept in
+ * registers; the trainer's envs are not touched) run `episodes` consecutive 50-step episodes
+ * under the mean action of the trainer's teacher or student.  Episode e of env i starts from
+ * reset draw draws[(e n_envs + i) 6 ..] (the table layout of rd_set_reset_mode) or, with draws
+ * NULL, from Philox(seed, env_base + i, first_episode + e); each of its 50 steps is
+ * observe -> forward -> env.step(unclipped mean).
+ * Same arithmetic as rdd_forward + rd_step: the outputs are bitwise those of the stepwise loop
+ * (rd_reset, then 50 x { rdd_forward on the observation, rd_step with the mean }), for the f32
+ * nets and for a RDD_DTYPE_BF16 trainer's student alike, independent of the launch's grid.
+ * Outputs (device, caller-owned; final_dist and records may be NULL):
+ *   returns    [episodes][n_envs]  sum of the episode's 50 step rewards, f32, in step order
+ *   final_dist [episodes][n_envs]  |fingertip - target| after the episode's last step
+ *   records    [episodes][n_envs][50][21]  one record per step in the dataset's layout
+ *              ob[11] | reward | t_pdflat[4] | s_pdflat[4] | stepped_with:
+ *              ob = the observation the policy saw; reward = the one this env's PREVIOUS step of
+ *              this call returned (0 for episode 0 step 0, carried over the reset for later
+ *              episodes' step 0); t_pdflat = the teacher's mean | logstd; teacher stepping:
+ *              s_pdflat = 0, stepped_with = 0 and the student is not run; student stepping:
+ *              s_pdflat = the student's, stepped_with = 1.
+ * No side effects on the trainer (env state, counters, Adam state, gradient, metrics).
+ * Asynchronous on the trainer's stream, no host sync, no allocation, no workspace: capturable.
+ * RD_EINVAL: NULL trainer, config or returns; n_envs < 1; episodes < 1; unknown policy;
+ * negative env_base, first_episode or grid (all checked before any device call). */
+#define RDD_EVAL_TEACHER 0
+#define RDD_EVAL_STUDENT 1
+typedef struct {
+    int64_t n_envs;          /* evaluation envs (their own states; not the trainer's)       */
+    int64_t env_base;        /* global id of evaluation env 0 (Philox key)                  */
+    uint64_t seed;           /* Philox reset seed                                           */
+    int32_t policy;          /* RDD_EVAL_*: whose mean action steps the envs                */
+    int32_t episodes;        /* E >= 1 consecutive episodes per env                         */
+    int32_t first_episode;   /* Philox episode index of the first one                       */
+    int32_t grid;            /* workgroups; 0 = auto                                        */
+    const float* draws;      /* NULL: Philox; else device table [E][n_envs][6] (q0 q1 v0 v1 tx ty) */
+} rdd_eval_config;
+int rdd_evaluate(rdd_trainer* tr, const rdd_eval_config* cfg, float* returns, float* final_dist, float* records);
+
 /* Env state hooks (state [8][n_envs] SoA, see reacher.h). */
 int rdd_get_env_state(rdd_trainer* tr, float* state);
 /* rdd_set_env_state checks the caller's joint angles first (host-synchronising): the fused

@@ -7,4 +7,4 @@ C ABI (include/reacher.h, include/reacher_distill.h), driven from Python on PyTo
 """
 from . import config  # noqa: F401
 
-__all__ = ["config", "env", "policy", "distill"]
+__all__ = ["config", "env", "policy", "distill", "evaluate"]

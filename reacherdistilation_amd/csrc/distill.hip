@@ -2031,6 +2031,145 @@ __global__ __launch_bounds__(FBLOCK) void forward_kernel(const float* tnet, cons
     }
 }
 
+// ---------------------------------------------------------------- whole-episode evaluation
+// rdd_evaluate: one launch rolls n evaluation envs through E consecutive 50-step episodes under
+// one policy's mean action (DESIGN.md §3 "Evaluation").  A wave owns a group of gs envs (64, or 16
+// for a small batch) for the whole launch: the state stays in registers (one env per lane), the
+// raw observations and the actions pass through a per-wave LDS scratch between the env-per-lane
+// physics and the 16-env MFMA tiles of the forward, the weights stay in LDS.  The arithmetic is
+// that of the stepwise path -- rd_reset / rd_step's rd::env_reset, rd::observe<true>,
+// rd::env_step<true>, and forward_kernel's mlp_forward / mlp_forward_bf16 on the same load_net
+// images -- and every env's chain is independent of its tile mates, so returns, final
+// distances and records are bitwise those of rdd_forward + rd_step, whatever gs and the grid.
+constexpr int EWAVES = 8, EBLOCK = 64 * EWAVES;
+constexpr int E_SO = 0;                          // [64][SOS] raw obs (component 11 = 1)
+constexpr int E_ACT = E_SO + GROUP * SOS;        // [64][2] the stepping policy's means
+constexpr int ESCR = E_ACT + GROUP * 2;
+constexpr int EREC = rd::kObsDim + 1 + 4 + 4 + 1;   // dataset.py's record: ob | reward | t_pdflat | s_pdflat | stepped_with
+constexpr int E_NS = NETB_S > NET ? NETB_S : NET;   // the student's forward image, f32 (no W2^T) or bf16
+constexpr int E_LDS = NET + E_NS + EWAVES * ESCR;
+static_assert(ESCR % 4 == 0 && E_NS % 4 == 0 && 2 * E_LDS * 4 <= 160 * 1024, "evaluation LDS: two workgroups per CU");
+
+struct EvalArgs {
+    int64_t n, env_base;
+    uint64_t seed;
+    const float* tnet;
+    const float* snet;
+    const float* draws;      // [E][n][6] or null (Philox)
+    float* returns;          // [E][n]
+    float* final_dist;       // [E][n] or null
+    float* records;          // [E][n][50][EREC] or null
+    int student, episodes, first_episode, gs;
+};
+
+// |fingertip - target| of the held kinematics, as rd::env_step's reward term computes it
+__device__ __forceinline__ float tip_distance(const rd::State& st) {
+    FP_SOURCE_ROUNDING();
+    return __builtin_amdgcn_sqrtf(st.dx * st.dx + st.dy * st.dy);
+}
+
+// f32 instance: <= 128 VGPRs, so that the two workgroups a CU's LDS holds are resident (4 waves
+// per SIMD: one wave's physics issues beside another's MFMAs); the bf16 instance would spill there
+template <bool BS>
+__global__ __launch_bounds__(EBLOCK, BS ? 2 : 4) void evaluate_kernel(EvalArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[E_LDS];
+    const bool run_t = !a.student || a.records, run_s = a.student != 0;
+    if (run_t) load_net(lds, a.tnet, false, EBLOCK);
+    if (run_s) {
+        if constexpr (BS) load_net_bf16(lds + NET, a.snet, EBLOCK);
+        else load_net(lds + NET, a.snet, false, EBLOCK);
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+    float* so = lds + NET + E_NS + wave * ESCR + E_SO;
+    float* sact = lds + NET + E_NS + wave * ESCR + E_ACT;
+    const float* LT = lds;
+    const float* LS = lds + NET;
+    const int64_t n = a.n, ngroups = (n + a.gs - 1) / a.gs;
+    for (int64_t grp = blockIdx.x + (int64_t)wave * gridDim.x; grp < ngroups; grp += (int64_t)gridDim.x * EWAVES) {
+        const int64_t base = grp * a.gs;
+        const int cnt = (int)(n - base < a.gs ? n - base : a.gs);   // envs of this group
+        const int ntile = (cnt + TILE - 1) / TILE;
+        const bool valid = lane < cnt;
+        const int64_t i = base + (valid ? lane : 0);
+        rd::State st;
+        float prev = 0.0f;   // the reward this env's previous step returned (records)
+        for (int e = 0; e < a.episodes; ++e) {
+            float d[6];
+            if (a.draws) {
+                const float* p = a.draws + ((int64_t)e * n + i) * 6;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) d[k] = p[k];
+            } else {
+                rd::philox_draw(a.seed, (uint64_t)(a.env_base + i), (uint32_t)(a.first_episode + e), d);
+            }
+            rd::env_reset(st, d);
+            float ret = 0.0f;
+            float* rec = a.records ? a.records + ((int64_t)e * n + i) * (rd::kEpisodeSteps * EREC) : nullptr;
+            for (int s = 0; s < rd::kEpisodeSteps; ++s) {
+                float ob[rd::kObsDim];
+                rd::observe<true>(st, ob);
+#pragma unroll
+                for (int k = 0; k < rd::kObsDim; ++k) so[lane * SOS + k] = ob[k];
+                so[lane * SOS + OBD] = 1.0f;
+                wave_sync();
+                for (int t = 0; t < ntile; ++t) {   // wave-uniform
+                    const float* tob = so + t * TILE * SOS;
+                    const bool out = g == 0 && t * TILE + j < cnt;
+                    float* trec = rec ? a.records + (((int64_t)e * n + base + t * TILE + (out ? j : 0)) *
+                                                     rd::kEpisodeSteps + s) * EREC + rd::kObsDim + 1
+                                      : nullptr;
+                    f32x4 H1[4], H2[4];
+                    float m0 = 0.0f, m1 = 0.0f;
+                    if (run_t) {
+                        // fenced (see mfma()): unfenced, hipcc issues the next k-steps' weight loads into
+                        // SrcC registers of in-flight f32 MFMAs here (hazards.py LDSRC, 11 sites); the
+                        // fence changes the schedule only, not a bit of the result
+                        mlp_forward<true>(LT, tob, j, g, H1, H2, m0, m1);
+                        if (trec && out) {
+                            trec[0] = m0; trec[1] = m1; trec[2] = LT[N_LS]; trec[3] = LT[N_LS + 1];
+                        }
+                    }
+                    if (run_s) {
+                        float ls0, ls1;
+                        if constexpr (BS) {
+                            mlp_forward_bf16(LS, tob, j, g, H1, H2, m0, m1);
+                            ls0 = LS[NB_LS]; ls1 = LS[NB_LS + 1];
+                        } else {
+                            mlp_forward<true>(LS, tob, j, g, H1, H2, m0, m1);
+                            ls0 = LS[N_LS]; ls1 = LS[N_LS + 1];
+                        }
+                        if (trec && out) {
+                            trec[4] = m0; trec[5] = m1; trec[6] = ls0; trec[7] = ls1;
+                        }
+                    } else if (trec && out) {
+                        trec[4] = 0.0f; trec[5] = 0.0f; trec[6] = 0.0f; trec[7] = 0.0f;
+                    }
+                    if (g == 0) {   // the tile's means: env-per-lane again through the scratch
+                        sact[(t * TILE + j) * 2] = m0;
+                        sact[(t * TILE + j) * 2 + 1] = m1;
+                    }
+                }
+                wave_sync();
+                const float a0 = valid ? sact[lane * 2] : 0.0f, a1 = valid ? sact[lane * 2 + 1] : 0.0f;
+                if (rec && valid) {
+                    float* r = rec + s * EREC;
+#pragma unroll
+                    for (int k = 0; k < rd::kObsDim; ++k) r[k] = ob[k];
+                    r[rd::kObsDim] = prev;
+                    r[EREC - 1] = a.student ? 1.0f : 0.0f;
+                }
+                prev = rd::env_step<true>(st, a0, a1);
+                ret += prev;
+            }
+            if (valid) {
+                a.returns[(int64_t)e * n + i] = ret;
+                if (a.final_dist) a.final_dist[(int64_t)e * n + i] = tip_distance(st);
+            }
+        }
+    }
+}
+
 int num_cus(int device) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 256;
@@ -2059,6 +2198,7 @@ struct rdd_trainer {
     unsigned long long* dbg = nullptr;   // RD_STAMPS builds only
     int last_grid = 0;                   // workgroups of the last rollout (rows of ws to reduce)
     int ws_rows = 0;                     // rows of ws (the device's CU count, or cfg.grid)
+    int cus = 0;                         // the device's CU count (rdd_evaluate's grid: no query per launch)
     int gs = GROUP;                      // envs per group of the env rollout
     int accum = 1;                       // rollouts per optimiser step (MSE normalisation)
     rd_comm* comm = nullptr;             // bound RCCL communicator (multi-GPU), not owned
@@ -2223,7 +2363,8 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
     t->accum = cfg->accum_steps > 1 ? cfg->accum_steps : 1;
     t->device = device;
     t->stream = (hipStream_t)hip_stream;
-    const int cap = cfg->grid > 0 ? cfg->grid : num_cus(device);
+    t->cus = num_cus(device);
+    const int cap = cfg->grid > 0 ? cfg->grid : t->cus;
     t->ws_rows = cap;
     t->gs = group_envs(cfg->n_envs, cap * PAIRS, cfg->group_envs);
     t->grid = grid_for(cfg->n_envs, t->gs, cap);
@@ -2460,6 +2601,44 @@ int rdd_forward(rdd_trainer* t, const float* obs, int64_t n, float* tflat, float
         hipLaunchKernelGGL(forward_kernel<false>, dim3((unsigned)blocks), dim3(FBLOCK), 0, t->stream, t->tnet,
                            t->snet, obs, n, tflat, sflat);
     RD_HIP(hipGetLastError(), "forward_kernel launch");
+    return RD_OK;
+}
+
+int rdd_evaluate(rdd_trainer* t, const rdd_eval_config* cfg, float* returns, float* final_dist, float* records) {
+    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "rdd_evaluate: null trainer, config or returns");
+    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
+        return rd::set_error(RD_EINVAL, "rdd_evaluate: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
+    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "rdd_evaluate: episodes %d < 1", cfg->episodes);
+    if (cfg->policy != RDD_EVAL_TEACHER && cfg->policy != RDD_EVAL_STUDENT)
+        return rd::set_error(RD_EINVAL, "rdd_evaluate: unknown policy %d", cfg->policy);
+    if (cfg->env_base < 0 || cfg->first_episode < 0 || cfg->grid < 0)
+        return rd::set_error(RD_EINVAL, "rdd_evaluate: negative env_base, first_episode or grid");
+    rd::DeviceGuard g(t->device);
+    RD_HIP(g.err, "rdd_evaluate: hipSetDevice");
+    EvalArgs a;
+    a.n = cfg->n_envs;
+    a.env_base = cfg->env_base;
+    a.seed = cfg->seed;
+    a.tnet = t->tnet;
+    a.snet = t->snet;
+    a.draws = cfg->draws;
+    a.returns = returns;
+    a.final_dist = final_dist;
+    a.records = records;
+    a.student = cfg->policy == RDD_EVAL_STUDENT;
+    a.episodes = cfg->episodes;
+    a.first_episode = cfg->first_episode;
+    // two workgroups fit a CU (LDS); below one 64-env group per resident wave, 16-env groups
+    // (one tile per wave and step) spread a small batch over the CUs, as group_envs() does
+    const int cap = cfg->grid > 0 ? cfg->grid : 2 * t->cus;
+    a.gs = a.n >= (int64_t)GROUP * cap * EWAVES ? GROUP : TILE;
+    const int64_t ngroups = (a.n + a.gs - 1) / a.gs;
+    const unsigned grid = (unsigned)(ngroups < cap ? ngroups : cap);
+    if (t->cfg.student_dtype == RDD_DTYPE_BF16)
+        hipLaunchKernelGGL(evaluate_kernel<true>, dim3(grid), dim3(EBLOCK), 0, t->stream, a);
+    else
+        hipLaunchKernelGGL(evaluate_kernel<false>, dim3(grid), dim3(EBLOCK), 0, t->stream, a);
+    RD_HIP(hipGetLastError(), "evaluate_kernel launch");
     return RD_OK;
 }
 

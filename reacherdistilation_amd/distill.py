@@ -38,7 +38,21 @@ class RddConfig(ctypes.Structure):
                 ("student_dtype", I32), ("accum_steps", I32), ("f32_split", I32), ("group_envs", I32)]
 
 
+class RddEvalConfig(ctypes.Structure):
+    _fields_ = [("n_envs", I64), ("env_base", I64), ("seed", U64), ("policy", I32), ("episodes", I32),
+                ("first_episode", I32), ("grid", I32), ("draws", P)]
+
+
+@dataclass
+class EvalResult:
+    """DistillTrainer.evaluate's outputs (device tensors; the optional ones None when not asked for)."""
+    returns: torch.Tensor                      # [E, n] f32: each episode's 50 step rewards summed in step order
+    final_dist: torch.Tensor | None = None     # [E, n] f32: |fingertip - target| after the episode's last step
+    records: torch.Tensor | None = None        # [E, n, 50, 21] f32 in dataset.py's record layout
+
+
 nat.register({
+    "rdd_evaluate": (INT, [P, ctypes.POINTER(RddEvalConfig), P, P, P]),
     "rdd_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RddConfig), INT, P]),
     "rdd_destroy": (INT, [P]),
     "rdd_param_count": (INT, []),
@@ -340,6 +354,42 @@ class DistillTrainer:
         nat.check(self._lib.rdd_forward(self._h, nat.ptr(obs), n, nat.ptr(t) if t is not None else None,
                                         nat.ptr(s) if s is not None else None), "rdd_forward")
         return t, s
+
+    def evaluate(self, policy: str = "student", n_envs: int = 4096, episodes: int = 1, *, seed: int | None = None,
+                 env_base: int = 0, first_episode: int = 0, draws=None, final_dist: bool = False,
+                 records: bool = False, grid: int = 0) -> EvalResult:
+        """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes under
+        the mean action of this trainer's ``policy`` ("teacher" | "student") in ONE launch
+        (rdd_evaluate): bitwise the result of the stepwise loop -- BatchedReacher.reset(), then 50 x
+        {forward, BatchedReacher.step(mean)} per episode -- with no side effect on the trainer.
+        Episode e of env i resets from ``draws[e, i]`` ([E, n_envs, 6]: q0 q1 v0 v1 tx ty, e.g.
+        env.gym_reset_draws per env) or, without a table, from Philox(seed, env_base + i,
+        first_episode + e).  ``seed=None`` is the trainer's seed: evaluation env i then repeats
+        training env i's resets, so held-out envs need another seed or an ``env_base`` past the
+        training range (>= the global env count).  Asynchronous on the trainer's stream
+        (set_stream); the launch needs no workspace and can be captured in a graph."""
+        if policy not in ACTORS:
+            raise ValueError(f"policy must be one of {sorted(ACTORS)}, got {policy!r}")
+        n, E = int(n_envs), int(episodes)
+        if n < 1 or E < 1:
+            raise ValueError("n_envs >= 1 and episodes >= 1")
+        table = None
+        if draws is not None:
+            table = torch.as_tensor(draws).to(self.device, torch.float32).contiguous()
+            if table.shape != (E, n, 6):
+                raise ValueError(f"draws must be [{E}, {n}, 6]")
+        kw = dict(dtype=torch.float32, device=self.device)
+        res = EvalResult(torch.empty(E, n, **kw),
+                         torch.empty(E, n, **kw) if final_dist else None,
+                         torch.empty(E, n, 50, 21, **kw) if records else None)
+        c = RddEvalConfig(n_envs=n, env_base=int(env_base), seed=(self.cfg.seed if seed is None else int(seed)) % 2 ** 64,
+                          policy=ACTORS[policy], episodes=E, first_episode=int(first_episode), grid=int(grid),
+                          draws=table.data_ptr() if table is not None else None)
+        nat.check(self._lib.rdd_evaluate(self._h, ctypes.byref(c), nat.ptr(res.returns),
+                                         nat.ptr(res.final_dist) if final_dist else None,
+                                         nat.ptr(res.records) if records else None), "rdd_evaluate")
+        self._keep = table   # the launch reads it asynchronously
+        return res
 
     def env_state(self) -> torch.Tensor:
         st = torch.empty(8, self.n_local, dtype=torch.float32, device=self.device)
