@@ -29,7 +29,8 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Werror",
           "-Wno-unused-function", "-munsafe-fp-atomics"]
 LDFLAGS = ["-shared", f"--offload-arch={ARCH}", "-ldl"]
-# Per-source flags.  distill.hip (the fused rollout) is compiled without SLP vectorisation: the
+# Per-source flags.  distill.hip (the fused rollout: one translation unit with the distill_*.h it
+# includes, rollout_kernel in distill_rollout.h) is compiled without SLP vectorisation: the
 # SLP pass packed the producer's dW3 / db3 accumulators into v_pk_fma_f32 / v_pk_add_f32 at the
 # tile loop's latch, whose operands the next tile's first LDS loads overwrite; on gfx950 a
 # packed-f32 op queued behind MFMAs can read its operands after such a load landed, and lanes

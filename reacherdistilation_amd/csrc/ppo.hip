@@ -26,6 +26,7 @@
 
 #include "../../include/reacher_ppo.h"
 #include "rd_common.h"
+#include "rd_device.h"
 #include "rd_physics.h"
 
 namespace {
@@ -212,12 +213,10 @@ static_assert(RA_COLS * RA_SLICES == 256 && (RA_SLICES & (RA_SLICES - 1)) == 0, 
 static_assert(MB_R == 32 && HID == 64 && PB1 == OBD * HID && VC1 == OBD * HID,
               "two 16-row MFMA blocks per tile; b1 follows W1");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// tanh as 1 - 2 / (e^{2|x|} + 1) with the sign of x: v_exp + v_rcp (|error| < 3e-7)
-__device__ __forceinline__ float tanh_fast(float x) {
+using rd::f32x4, rd::mfma;
+// tanh as 1 - 2 / (e^{2|x|} + 1) with the sign of x: v_exp + v_rcp (|error| < 3e-7).  Not
+// rd::tanh_fast (1 - 2 / (2^y + 1), no sign handling): the two round differently.
+__device__ __forceinline__ float tanh_abs(float x) {
     const float t = 1.0f - __fdividef(2.0f, __expf(2.0f * fabsf(x)) + 1.0f);
     return copysignf(t, x);
 }
@@ -293,12 +292,12 @@ __device__ __forceinline__ void mb_forward(MbLds& L, int net, int r0, int lr, in
         c[cb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < 3; ++s)
-            c[cb] = mfma4(L.z[r0 + lr][4 * s + lk], L.w1[net][(4 * s + lk) * HID + 16 * cb + lr], c[cb]);
+            c[cb] = mfma(L.z[r0 + lr][4 * s + lk], L.w1[net][(4 * s + lk) * HID + 16 * cb + lr], c[cb]);
     }
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) L.h1[net][r0 + 4 * lk + i][16 * cb + lr] = tanh_fast(c[cb][i]);
+        for (int i = 0; i < 4; ++i) L.h1[net][r0 + 4 * lk + i][16 * cb + lr] = tanh_abs(c[cb][i]);
     __syncthreads();
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
@@ -309,12 +308,12 @@ __device__ __forceinline__ void mb_forward(MbLds& L, int net, int r0, int lr, in
     for (int s = 0; s < HID / 4; ++s) {
         const float av = L.h1[net][r0 + lr][4 * s + lk];
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb) c[cb] = mfma4(av, L.w2[net][(4 * s + lk) * W2LD + 16 * cb + lr], c[cb]);
+        for (int cb = 0; cb < 4; ++cb) c[cb] = mfma(av, L.w2[net][(4 * s + lk) * W2LD + 16 * cb + lr], c[cb]);
     }
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) L.h2[net][r0 + 4 * lk + i][16 * cb + lr] = tanh_fast(c[cb][i]);
+        for (int i = 0; i < 4; ++i) L.h2[net][r0 + 4 * lk + i][16 * cb + lr] = tanh_abs(c[cb][i]);
 }
 
 // the heads of row r (after the barrier that follows mb_forward)
@@ -362,6 +361,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutArgs a) {
     int step = 0, epi = 0;
     float ret = 0.f, newf = 0.f, it_ret = 0.f, it_eps = 0.f;
     if (envl) {
+        // (not rd::load_state / store_state: their (state + k n) + e addressing changes this kernel's schedule)
         st.q0 = a.state[e]; st.q1 = a.state[n + e]; st.v0 = a.state[2 * n + e]; st.v1 = a.state[3 * n + e];
         st.tx = a.state[4 * n + e]; st.ty = a.state[5 * n + e]; st.dx = a.state[6 * n + e]; st.dy = a.state[7 * n + e];
         step = a.ep_step[e]; epi = a.ep_idx[e]; ret = a.ep_ret[e]; newf = a.new_next[e];
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
         for (int s = 0; s < HID / 4; ++s) {
             const float av = L.d2[net][r0 + lr][4 * s + lk];
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) c[cb] = mfma4(av, L.w2[net][(16 * cb + lr) * W2LD + 4 * s + lk], c[cb]);
+            for (int cb = 0; cb < 4; ++cb) c[cb] = mfma(av, L.w2[net][(16 * cb + lr) * W2LD + 4 * s + lk], c[cb]);
         }
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
@@ -599,8 +599,8 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb) {
                 const float d = L.d2[net][4 * s + lk][16 * jb + lr];
-                a2[0][jb] = mfma4(h0, d, a2[0][jb]);
-                a2[1][jb] = mfma4(h1, d, a2[1][jb]);
+                a2[0][jb] = mfma(h0, d, a2[0][jb]);
+                a2[1][jb] = mfma(h1, d, a2[1][jb]);
             }
         }
         if (half == 0) {
@@ -613,7 +613,7 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
         for (int s = 0; s < MB_R / 4; ++s) {
             const float zv = L.z[4 * s + lk][lr];
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) a1[jj] = mfma4(zv, L.d1[net][4 * s + lk][32 * half + 16 * jj + lr], a1[jj]);
+            for (int jj = 0; jj < 2; ++jj) a1[jj] = mfma(zv, L.d1[net][4 * s + lk][32 * half + 16 * jj + lr], a1[jj]);
         }
         __syncthreads();
     }
@@ -711,13 +711,13 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(RaArgs a) {
     if (p < P_ALL) {
         const float g = lsc ? (float)d0 : g0;
         a.grad[p] = g;
-        const float alpha = a.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
+        const float alpha = rd::adam_alpha(a.lr, b1p, b2p);
         float m = m0, v = v0;
-        m += (g - m) * (1.0f - a.b1);
-        v += (g * g - v) * (1.0f - a.b2);
+        m = rd::adam_m(g, m, a.b1);
+        v = rd::adam_v(g, v, a.b2);
         a.m[p] = m;
         a.v[p] = v;
-        a.params[p] = x0 - (m * alpha) / (sqrtf(v) + a.eps);
+        a.params[p] = x0 - rd::adam_delta(m, v, alpha, a.eps);
     }
     if (blockIdx.x == 0) {
         if (a.accumulate && c < 3) a.acc[c] += d0;
@@ -752,8 +752,7 @@ __global__ void reset_envs_kernel(int64_t n, int64_t env_base, uint64_t seed, fl
     rd::philox_draw(seed, (uint64_t)(env_base + e), 0u, d);
     rd::State st;
     rd::env_reset(st, d);
-    state[e] = st.q0; state[n + e] = st.q1; state[2 * n + e] = st.v0; state[3 * n + e] = st.v1;
-    state[4 * n + e] = st.tx; state[5 * n + e] = st.ty; state[6 * n + e] = st.dx; state[7 * n + e] = st.dy;
+    rd::store_state(state, n, e, st);
     ep_step[e] = 0;
     ep_idx[e] = 0;
     ep_ret[e] = 0.0f;
@@ -925,8 +924,7 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
     t->cfg = *cfg;
     if (t->cfg.metrics_len == 0) t->cfg.metrics_len = 1024;
     t->device = device;
-    hipDeviceProp_t prop;
-    t->cus = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
+    t->cus = rd::cu_count(device);
     t->stream = (hipStream_t)hip_stream;
     t->n = cfg->n_envs;
     t->S = S;

@@ -37,6 +37,12 @@ struct DeviceGuard {
     }
 };
 
+// CUs of `device` (256, an MI355X's, if the query fails): grid caps and partial-row counts
+inline int cu_count(int device) {
+    hipDeviceProp_t prop;
+    return hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
+}
+
 }  // namespace rd
 
 #define RD_HIP(call, what)                                \

@@ -20,9 +20,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rd_device.h"
+
 namespace rdg {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rd::f32x4;
 
 enum { EPI_NONE = 0, EPI_TANH = 1, EPI_DTANH = 2, EPI_LSTM_BWD = 3 };
 

@@ -48,6 +48,23 @@ struct State {
     float q0, q1, v0, v1, tx, ty, dx, dy;   // (dx,dy) = fingertip - target at the held kinematics
 };
 
+// The state array in HBM is SoA [kStateDim][n]: row k of env i is (s + k n)[i], a uniform 64-bit
+// row base plus the lane's index of type I (32-bit where n <= 2^31 lets it be).
+template <class I>
+__device__ __forceinline__ void load_state(const float* s, int64_t n, I i, State& st) {
+    st.q0 = *(s + 0 * n + i); st.q1 = *(s + 1 * n + i); st.v0 = *(s + 2 * n + i); st.v1 = *(s + 3 * n + i);
+    st.tx = *(s + 4 * n + i); st.ty = *(s + 5 * n + i); st.dx = *(s + 6 * n + i); st.dy = *(s + 7 * n + i);
+}
+// NT: non-temporal stores (a state written once per step and read by a later kernel).
+// target_too: the target rows change only at a reset.
+template <bool NT = false, class I>
+__device__ __forceinline__ void store_state(float* s, int64_t n, I i, const State& st, bool target_too = true) {
+    const auto put = [](float* p, float v) { if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v; };
+    put(s + 0 * n + i, st.q0); put(s + 1 * n + i, st.q1); put(s + 2 * n + i, st.v0); put(s + 3 * n + i, st.v1);
+    if (target_too) { put(s + 4 * n + i, st.tx); put(s + 5 * n + i, st.ty); }
+    put(s + 6 * n + i, st.dx); put(s + 7 * n + i, st.dy);
+}
+
 // sin and cos together for the joint angles.  Cody-Waite reduction by pi/2 with a 3-part
 // constant (fma, exact k*C1 for |x| < 8192 rad) and Cephes' minimax polynomials on
 // [-pi/4, pi/4]: <= 2 ulp, ~20 VALU instead of the ~45 of the libm path.  With kWideRange
@@ -77,7 +94,6 @@ __device__ __forceinline__ void sincos_acc(float x, float* s, float* c) {
     *s = (q & 2) ? -sv : sv;
     *c = ((q + 1) & 2) ? -cv : cv;
 }
-
 
 // sin and cos of a JOINT-1 angle (q1, the RK4 stage angles, the held kinematics' kq1): the
 // hardware v_sin_f32 / v_cos_f32 (argument in revolutions).  Joint 1 is limited to +-3 rad (a soft

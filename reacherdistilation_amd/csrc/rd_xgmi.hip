@@ -38,13 +38,14 @@
 #include "../../include/reacher_comm.h"
 #include "rd_comm_impl.h"
 #include "rd_common.h"
+#include "rd_device.h"
 
 namespace {
 
 constexpr int XG_BLOCK = 256;
 constexpr int XG_FLAGS_BYTES = 256;                 // flags[2][RD_XG_MAX] (uint32), the poison word, padded
 constexpr int XG_POISON = 2 * RD_XG_MAX;            // uint32 index of the poison word in the flags area
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rd::f32x4;
 constexpr int XG_UNROLL = 8;                        // float4 per thread issued at once: n <= 8,192
 
 struct XgArgs {

@@ -26,7 +26,6 @@ constexpr int kBlock = 256;
 // kernel, so they are stored non-temporal: +1 % at 16.8M envs, +3.5 % at 4.2M, +4.5 % at 1M
 // against plain stores (profiles/r03n_env_nt.txt; same bits).
 template <class T> __device__ __forceinline__ void ost(T* p, T v) { __builtin_nontemporal_store(v, p); }
-template <class T> __device__ __forceinline__ T ild(const T* p) { return *p; }
 
 struct ResetSrc {
     int mode;              // RD_RESET_PHILOX / RD_RESET_TABLE
@@ -45,20 +44,6 @@ __device__ __forceinline__ void draw_reset(const ResetSrc& src, int64_t n, int64
     } else {
         rd::philox_draw(src.seed, (uint64_t)(src.env_base + i), (uint32_t)episode, d);
     }
-}
-
-__device__ __forceinline__ rd::State load_state(const float* __restrict__ s, int64_t n, int64_t i) {
-    rd::State st;
-    st.q0 = ild(s + 0 * n + i); st.q1 = ild(s + 1 * n + i); st.v0 = ild(s + 2 * n + i); st.v1 = ild(s + 3 * n + i);
-    st.tx = ild(s + 4 * n + i); st.ty = ild(s + 5 * n + i); st.dx = ild(s + 6 * n + i); st.dy = ild(s + 7 * n + i);
-    return st;
-}
-
-__device__ __forceinline__ void store_state(float* __restrict__ s, int64_t n, int64_t i, const rd::State& st,
-                                            bool target_too) {
-    ost(s + 0 * n + i, st.q0); ost(s + 1 * n + i, st.q1); ost(s + 2 * n + i, st.v0); ost(s + 3 * n + i, st.v1);
-    if (target_too) { ost(s + 4 * n + i, st.tx); ost(s + 5 * n + i, st.ty); }
-    ost(s + 6 * n + i, st.dx); ost(s + 7 * n + i, st.dy);
 }
 
 // Write this block's obs rows [base, base+cnt) x 11 via an LDS transpose: lane-strided
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void rd_reset_kernel(int64_t n, float* __re
         draw_reset(src, n, i, episode, d);
         rd::State st;
         rd::env_reset(st, d);
-        store_state(state, n, i, st, true);
+        rd::store_state<true>(state, n, i, st);
         rd::observe(st, ob);
     }
     write_obs(obs, base, cnt, ob, lds);
@@ -113,16 +98,17 @@ __global__ __launch_bounds__(kBlock) void rd_step_kernel(int64_t n, float* __res
     const int cnt = (int)min((int64_t)kBlock, n - base);
     float ob[11];
     if (i < n) {
-        rd::State st = load_state(state, n, i);
+        rd::State st;
+        rd::load_state(state, n, i, st);
         typedef float v2f __attribute__((ext_vector_type(2)));
-        const v2f a = ild(reinterpret_cast<const v2f*>(act) + i);
+        const v2f a = reinterpret_cast<const v2f*>(act)[i];
         const float r = rd::env_step(st, a[0], a[1]);
         if (done_step) {
             float d[6];
             draw_reset(src, n, i, next_episode, d);
             rd::env_reset(st, d);
         }
-        store_state(state, n, i, st, done_step != 0);
+        rd::store_state<true>(state, n, i, st, done_step != 0);
         rd::observe(st, ob);
         ost(rew + i, r);
         ost(done + i, (uint8_t)(done_step != 0));

@@ -31,6 +31,7 @@
 
 #include "../../include/reacher_student_lstm.h"
 #include "rd_common.h"
+#include "rd_device.h"
 #include "rd_gemm.h"
 #include "rd_physics.h"
 
@@ -274,25 +275,9 @@ constexpr int PR_PHASE_BITS = 12;
 constexpr int PR_MAX_T = 1 << PR_PHASE_BITS;
 __device__ __forceinline__ uint32_t gr_tag(uint32_t gen, uint32_t phase) { return (gen << PR_PHASE_BITS) | phase; }
 
-// SrcC fence around MFMA chains (student_mlp.hip's fence_begin / fence_end): every operand is
-// in registers before the chains start, the accumulators pass through an empty asm
-// (memory clobber) before and after them and are read by a VALU before the closing one, so no
-// load issues while one of these f32 MFMAs is in flight -- hipcc otherwise renames a chain's
-// accumulators and loads the next operands into registers an in-flight MFMA still reads as SrcC
-// (scripts/isa/hazards.py class LDSRC; found in the sixteen-wave head backward, round 5).  Used by
-// the head's data gradients and the persistent BPTT's weight-gradient chains.
-template <int Q>
-__device__ __forceinline__ void fence_begin(rdg::f32x4 (&G)[Q]) {
-#pragma unroll
-    for (int t = 0; t < Q; ++t) asm volatile("" : "+v"(G[t])::"memory");
-}
-template <int Q>
-__device__ __forceinline__ void fence_end(rdg::f32x4 (&G)[Q]) {
-#pragma unroll
-    for (int t = 0; t < Q; ++t) G[t][3] = __builtin_amdgcn_fmed3f(G[t][3], G[t][3], G[t][3]);
-#pragma unroll
-    for (int t = 0; t < Q; ++t) asm volatile("" : "+v"(G[t])::"memory");
-}
+// SrcC fence around MFMA chains (rd_device.h), every operand in registers before they start: the
+// head's data gradients (sixteen-wave head backward, round 5), the persistent BPTT's weight gradients
+using rd::fence_begin, rd::fence_end;
 // bar: [0] the forward's finished-workgroup count, [1] the BPTT's barrier counter, [2] timeout
 // flag, [3] granule generation.  The last forward workgroup to finish (every one has read the
 // generation by then) resets [0] and [1] and advances [3], so the next call's tags are new.
@@ -1446,13 +1431,13 @@ struct AdamArgs {
 // into their packed copy
 __device__ __forceinline__ void adam_param(const AdamArgs& a, int p, float g, float b1p, float b2p) {
     {
-        const float alpha = a.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
+        const float alpha = rd::adam_alpha(a.lr, b1p, b2p);
         float m = a.m[p], v = a.v[p];
-        m += (g - m) * (1.0f - a.b1);
-        v += (g * g - v) * (1.0f - a.b2);
+        m = rd::adam_m(g, m, a.b1);
+        v = rd::adam_v(g, v, a.b2);
         a.m[p] = m;
         a.v[p] = v;
-        const float w = a.params[p] - (m * alpha) / (sqrtf(v) + a.eps);
+        const float w = a.params[p] - rd::adam_delta(m, v, alpha, a.eps);
         a.params[p] = w;
         if (p >= OFF_H) {
             const int q = p - OFF_H, ts = q / HSZ, x = hw_index(q - ts * HSZ);
@@ -1477,12 +1462,6 @@ __global__ void init_ctl_kernel(uint32_t* ctl, float b1, float b2) {
         const int o = 4 * threadIdx.x;
         ctl[o] = 0u; ctl[o + 1] = __float_as_uint(b1); ctl[o + 2] = __float_as_uint(b2); ctl[o + 3] = 0u;
     }
-}
-
-int cu_count(int device) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 256;
-    return prop.multiProcessorCount;
 }
 
 constexpr int64_t SPLIT_FLOATS = 16 << 20;  // split-K partials (64 MB)
@@ -1817,7 +1796,7 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
     t->cfg = *cfg;
     if (t->cfg.metrics_len == 0) t->cfg.metrics_len = 4096;
     t->device = device;
-    t->cus = cu_count(device);
+    t->cus = rd::cu_count(device);
     t->stream = (hipStream_t)hip_stream;
     t->T = cfg->steps;
     t->np = params_of(t->T);

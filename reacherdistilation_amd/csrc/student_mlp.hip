@@ -27,11 +27,12 @@
 
 #include "../../include/reacher_student_mlp.h"
 #include "rd_common.h"
+#include "rd_device.h"
 #include "rd_physics.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rd::f32x4, rd::mfma, rd::ld4, rd::wave_sum, rd::tanh_fast, rd::fence_begin, rd::fence_end;
 
 namespace sm {
 
@@ -101,18 +102,6 @@ static_assert(S_X0 == KP[0] + 4 && S_X1 == KP[1] + 4 && S_X2 == KP[2] + 4 && S_X
 
 using namespace sm;
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float tanh_fast(float z) {
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z * 2.8853900817779268f) + 1.0f), 1.0f);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Output blocks of a [ROWS x 16*NCB] result (RB = ROWS / 16), split over the 8 waves: for
 // NCB >= 8 a wave owns NCB/8 column blocks x all RB row blocks (the B operand is shared by
 // its row blocks); for NCB < 8 a wave owns at most one block.
@@ -125,8 +114,6 @@ struct Part {
     __device__ static int rb(int wave, int r) { return NCB >= WAVES ? r : wave % RB; }
     __device__ static int cb(int wave, int c) { return NCB >= WAVES ? wave * CPW + c : wave / RB; }
 };
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // Forward of layer L: Y[row][pk(c)] = act(b[c] + sum_k X[row][k] W[k][c]), c = 16 cb + i.
 template <int RB, int L, int SI, int SO>
@@ -225,26 +212,8 @@ struct WG {
     __device__ static bool ok(int wave, int t) { return KBN % STEP == 0 || kb(wave, t) < KBN; }
 };
 
-// SrcC fence around one k-step's MFMAs (as distill.hip's fence_begin/fence_end): the
-// accumulators pass through an empty asm (memory clobber) before and after them, and each is
-// read by a VALU before the closing asm, so no LDS load issues while one of these 8-pass f32
-// MFMAs is in flight.  Without it hipcc rotates the accumulators (D = v[20:23], C = v[22:25])
-// and issues the next k-step's operand loads into registers an in-flight MFMA still reads as
-// SrcC, 0-9 wait states after it (scripts/isa/hazards.py class LDSRC; such a load is lost for
-// lanes 48-63 when the MFMA is held in the pipe).
-template <int Q>
-__device__ __forceinline__ void fence_begin(f32x4 (&G)[Q]) {
-#pragma unroll
-    for (int t = 0; t < Q; ++t) asm volatile("" : "+v"(G[t])::"memory");
-}
-template <int Q>
-__device__ __forceinline__ void fence_end(f32x4 (&G)[Q]) {
-#pragma unroll
-    for (int t = 0; t < Q; ++t) G[t][3] = __builtin_amdgcn_fmed3f(G[t][3], G[t][3], G[t][3]);
-#pragma unroll
-    for (int t = 0; t < Q; ++t) asm volatile("" : "+v"(G[t])::"memory");
-}
-
+// Each k-step's MFMAs are SrcC-fenced (rd_device.h): unfenced, hipcc issues the next k-step's
+// operand loads into registers an in-flight MFMA still reads as SrcC.
 template <int ROWS, int L, int SH, int SD>
 __device__ __forceinline__ void wgrad_layer(const float* H, const float* D, f32x4 (&G)[WG<L>::Q], int wave, int i,
                                             int g) {
@@ -541,13 +510,13 @@ __global__ __launch_bounds__(ADAM_BLOCK) void reduce_adam_kernel(AdamArgs a) {
             gsum = p < P_REF ? a.grad[p] : 0.f;
         }
         if (a.adam && p < P_REF) {   // TF1 ApplyAdam (mlp_train.py:75-80)
-            const float alpha = a.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
+            const float alpha = rd::adam_alpha(a.lr, b1p, b2p);
             float m = a.m[p], v = a.v[p];
-            m += (gsum - m) * (1.0f - a.b1);
-            v += (gsum * gsum - v) * (1.0f - a.b2);
+            m = rd::adam_m(gsum, m, a.b1);
+            v = rd::adam_v(gsum, v, a.b2);
             a.m[p] = m;
             a.v[p] = v;
-            const float w = a.params[p] - (m * alpha) / (sqrtf(v) + a.eps);
+            const float w = a.params[p] - rd::adam_delta(m, v, alpha, a.eps);
             a.params[p] = w;
             store_param(a.img, ix, w);
         }
@@ -564,12 +533,6 @@ __global__ void init_ctl_kernel(uint32_t* ctl, float b1, float b2) {
         const int o = 4 * threadIdx.x;
         ctl[o] = 0u; ctl[o + 1] = __float_as_uint(b1); ctl[o + 2] = __float_as_uint(b2); ctl[o + 3] = 0u;
     }
-}
-
-int cu_count(int device) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 256;
-    return prop.multiProcessorCount;
 }
 
 }  // namespace
@@ -674,7 +637,7 @@ int rdm_create(rdm_trainer** out, const rdm_config* cfg, int device, void* hip_s
     if (t->cfg.metrics_len == 0) t->cfg.metrics_len = 4096;
     t->device = device;
     t->stream = (hipStream_t)hip_stream;
-    t->grid = cfg->grid > 0 ? cfg->grid : cu_count(device);
+    t->grid = cfg->grid > 0 ? cfg->grid : rd::cu_count(device);
     t->last_grid = 0;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) {

@@ -3,8 +3,9 @@
 ("split the VALU count by role and phase").
 
 Reads an ISA file compiled with line tables (hipcc -O3 -g ... --cuda-device-only -S): every
-instruction is attributed to the source function its `.loc` line falls in (distill.hip's
-helpers and kernel sections, rd_physics.h's functions), and every basic block gets an execution
+instruction is attributed to the source function its `.loc` line falls in, read from the file that
+`.loc` names (distill.hip and the distill_*.h it includes: helpers and kernel sections;
+rd_physics.h, rd_device.h: functions, prefixed with the header's name), and every basic block gets an execution
 weight from the control flow: natural loops are found from the back-edges, and a block runs
 `trips ** depth` times per wave for the loop depth it sits at (trips given per depth, e.g. 4 groups
 per pair and 4 tiles per group at c4).  Static attribution, so the weights are the kernel's
@@ -13,6 +14,7 @@ compare with.
 
 usage: valu_roles.py ISA.s SYMBOL_SUBSTRING DEPTH_TRIPS(e.g. 4,4) [SOURCE.hip]"""
 import collections
+import os
 import re
 import sys
 
@@ -20,10 +22,14 @@ sys.path.insert(0, __file__.rsplit("/", 1)[0])
 import hazards as hz  # noqa: E402
 
 SRC_DEFAULT = "reacherdistilation_amd/csrc/distill.hip"
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "reacherdistilation_amd", "csrc")
 
 
 def function_ranges(src):
-    """[(start_line, name)] of the device functions / lambdas / kernel sections of a source."""
+    """[(start_line, name)] of the device functions / lambdas / kernel sections of a source
+    ([] for a file that is not there, e.g. a ROCm header)."""
+    if not os.path.exists(src):
+        return []
     out = []
     pat = re.compile(r"^\s*(?:template\s*<[^>]*>\s*)?(?:__device__|__global__)[^(]*?\b(\w+)\s*\(")
     for i, l in enumerate(open(src).read().split("\n"), 1):
@@ -58,7 +64,7 @@ def main():
     for l in lines:
         m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"\s+"([^"]*)"', l)
         if m:
-            files[int(m.group(1))] = m.group(3)
+            files[int(m.group(1))] = (m.group(2), m.group(3))
     # the function's lines with their .loc
     name = next(n for n in hz.functions(path) if sym in n)
     start = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
@@ -95,8 +101,17 @@ def main():
                     stack.extend(p for p in pred[x] if p not in body)
                 for x in body:
                     depth[x] += 1
-    ranges = function_ranges(src)
-    hranges = {}
+    # the source and the parts it is split into (distill.hip, distill_*.h) give plain roles, any
+    # other file's functions carry its name
+    stem = os.path.basename(src).rsplit(".", 1)[0]
+    ranges = {}
+
+    def ranges_of(fdir, fn):   # the file as the ISA names it, else its name beside the source / in csrc
+        if (fdir, fn) not in ranges:
+            cands = [os.path.join(fdir, fn)] + [os.path.join(x, os.path.basename(fn)) for x in (os.path.dirname(src), CSRC)]
+            ranges[(fdir, fn)] = function_ranges(next((p for p in cands if os.path.exists(p)), cands[0]))
+        return ranges[(fdir, fn)]
+
     per_role = collections.Counter()
     per_role_static = collections.Counter()
     mfma_w = 0.0
@@ -111,15 +126,10 @@ def main():
             continue
         if not op.startswith("v_"):
             continue
-        fn = files.get(f, "?")
-        if fn.endswith(src.rsplit("/", 1)[-1]):
-            role = role_of(ranges, line)
-        else:
-            if fn not in hranges:
-                import os
-                h = "reacherdistilation_amd/csrc/" + fn
-                hranges[fn] = function_ranges(h) if os.path.exists(h) else []
-            role = fn.rsplit(".", 1)[0] + ":" + role_of(hranges[fn], line)
+        fdir, fn = files.get(f, ("", "?"))
+        role = role_of(ranges_of(fdir, fn), line)
+        if not os.path.basename(fn).startswith(stem):
+            role = os.path.basename(fn).rsplit(".", 1)[0] + ":" + role
         if op.startswith(hz.TRANS):
             role += " [trans]"
         per_role[role] += w
