@@ -22,7 +22,9 @@ Parameter vectors here: pol = the 5,060-float MlpPolicy layout of policy_np (W1 
 W3 b3 logstd); vf = V1[11][64] c1 V2[64][64] c2 V3[64][1] c3 (4,993 floats).
 
 Parity status: UNPINNED beyond the formulas (TensorFlow/baselines absent; no reference test
-covers PPO); checked by finite differences in tests/test_ppo_oracle.py.
+covers PPO); checked by finite differences in tests/test_ppo_oracle.py.  The minibatch
+shuffles (mt19937_64, shuffles) are the trainer's own, not baselines': pinned to the C++
+standard's check value and to a libstdc++ table (tests/golden/ppo_shuffles.json).
 """
 from __future__ import annotations
 
@@ -165,6 +167,47 @@ def loss_and_grads(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
     ent = (fp["logstd"] + 0.5 * np.log(2 * np.pi * np.e)).sum()
     kl = None
     return dict(pol_surr=pol_surr, vf_loss=vf_loss, ent=ent, gpol=gpol, gvf=gvf, ratio=ratio, kl=kl)
+
+
+def mt19937_64(seed):
+    """std::mt19937_64 (Matsumoto & Nishimura's 64-bit Mersenne Twister with the standard
+    constants) as a generator of its outputs."""
+    M64 = (1 << 64) - 1
+    NN, MM, UM, LM = 312, 156, 0xFFFFFFFF80000000, 0x7FFFFFFF
+    mt = [seed & M64]
+    for i in range(1, NN):
+        mt.append((6364136223846793005 * (mt[-1] ^ (mt[-1] >> 62)) + i) & M64)
+    while True:
+        for i in range(NN):
+            x = (mt[i] & UM) | (mt[(i + 1) % NN] & LM)
+            mt[i] = mt[(i + MM) % NN] ^ (x >> 1) ^ (0xB5026F5AA96619E9 if x & 1 else 0)
+        for x in mt:
+            x ^= (x >> 29) & 0x5555555555555555
+            x ^= (x << 17) & 0x71D67FFFEDA60000
+            x ^= (x << 37) & 0xFFF7EEE000000000
+            yield x ^ (x >> 43)
+
+
+def shuffles(seed, iteration, S, epochs):
+    """The trainer's minibatch shuffles of one iteration, [epochs, S]: one mt19937_64 seeded
+    with seed * 0x9E3779B97F4A7C15 + iteration + 1 (mod 2^64) runs on across the epochs; each
+    epoch is a Fisher-Yates shuffle of the identity from the top (j = rng() % (i + 1))."""
+    rng = mt19937_64((seed * 0x9E3779B97F4A7C15 + iteration + 1) & ((1 << 64) - 1))
+    out = np.zeros((epochs, S), np.int64)
+    for e in range(epochs):
+        p = list(range(S))
+        for i in range(S - 1, 0, -1):
+            j = next(rng) % (i + 1)
+            p[i], p[j] = p[j], p[i]
+        out[e] = p
+    return out
+
+
+def adam(n):
+    """MpiAdam as learn() builds it: policy_np.AdamTF1 with epsilon 1e-5 over [pol | vf]; the
+    caller sets ``lr = optim_stepsize * lrmult`` (a float32) before each step."""
+    from oracle.policy_np import AdamTF1
+    return AdamTF1(n, eps=1e-5)
 
 
 def total_loss(pol, vf, z, a, logp_old, atarg, ret, clip_eps):

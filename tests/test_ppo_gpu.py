@@ -69,11 +69,14 @@ def test_actor_batch_matches_oracle():
     np.testing.assert_allclose(std, rms.std, rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.parametrize("n,T", [(256, 64), (255, 63), (1, 50), (3, 7)])
+@pytest.mark.parametrize("n,T", [(256, 64), (255, 63), (1, 50), (3, 7), (300, 7), (1040, 32)])
 def test_full_batch_gradient_matches_oracle(n, T):
     """One minibatch over the whole actor batch: 512 / 503 32-row tiles (more than the 256
     workgroups of minibatch_kernel, so workgroups carry sums over several tiles; 255 x 63 ends
-    in a ragged tile), and 2 / 1 tiles (50 and 21 rows: padded rows must add nothing)."""
+    in a ragged tile), and 2 / 1 tiles (50 and 21 rows: padded rows must add nothing).
+    300 x 7: two GAE blocks feed the advantage moments.  1040 x 32: 1,040 tiles, more than
+    logp_old_kernel's 1,024 workgroups, so 16 of them loop; a wrong old log-probability on the
+    looped tiles makes the kernel's ratio differ from 1 against the oracle's own logp_old."""
     tr = _trainer(n_envs=n, horizon=T, optim_epochs=1, optim_batchsize=0)
     tr.iterate()                                         # one update: the policy moves off the rollout policy
     pol, vf = tr.policy().cpu().numpy(), tr.value().cpu().numpy()

@@ -2,6 +2,9 @@
 gradient by finite differences (ratios inside and outside the clip range), GAE against its
 definition, RunningMeanStd's moments.  Parity of PPO itself is UNPINNED by the reference
 (baselines/TF absent, no reference test): these pin the restatement to the formulas."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -87,3 +90,53 @@ def test_running_mean_std():
     c = 1000 + 1e-2
     np.testing.assert_allclose(rms.mean, x.sum(0) / c)
     np.testing.assert_allclose(rms.std, np.sqrt((1e-2 + (x ** 2).sum(0)) / c - (x.sum(0) / c) ** 2))
+
+
+def test_mt19937_64_check_value():
+    """The C++ standard's own check ([rand.predef]): the 10,000th consecutive invocation of a
+    default-constructed mt19937_64 (seed 5489) produces 9981545732273789042."""
+    g = pp.mt19937_64(5489)
+    for _ in range(9999):
+        next(g)
+    assert next(g) == 9981545732273789042
+
+
+def test_shuffles_match_the_host_program():
+    """tests/golden/ppo_shuffles.json holds the output of a stand-alone host C++ program
+    (libstdc++): for each (seed, iteration, S, epochs) it constructs
+    ``std::mt19937_64 rng(seed * 0x9E3779B97F4A7C15ull + iteration + 1)`` in uint64_t
+    arithmetic and, per epoch, fills ``p[i] = i`` and runs ``for (i = S - 1; i > 0; --i)
+    { j = rng() % (uint64_t)(i + 1); swap(p[i], p[j]); }`` without reseeding between epochs,
+    printing each epoch's ``p``: the loop of the trainer's draw_perms.  The cases have a seed
+    with a non-zero high word, a seed whose product wraps, iteration > 0, and more than 312
+    draws (the generator's state is regenerated)."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "ppo_shuffles.json")) as f:
+        cases = json.load(f)
+    assert len(cases) == 3
+    for c in cases:
+        got = pp.shuffles(c["seed"], c["iteration"], c["S"], c["epochs"])
+        np.testing.assert_array_equal(got, np.array(c["perm"]))
+        for row in got:
+            np.testing.assert_array_equal(np.sort(row), np.arange(c["S"]))
+    a = pp.shuffles(11, 0, 10, 2)
+    assert not np.array_equal(a, pp.shuffles(11, 1, 10, 2))       # the iteration enters the seed
+    assert not np.array_equal(a[0], a[1])                         # the generator runs on across epochs
+
+
+def test_ppo_adam_is_adamtf1_with_eps_1e_5():
+    """pp.adam: policy_np.AdamTF1 (pinned to the reference's graph) with MpiAdam's epsilon and
+    a per-step lr; one step against the formula in f64, and the beta powers carry."""
+    opt = pp.adam(5)
+    assert isinstance(opt, pn.AdamTF1) and opt.eps == np.float32(1e-5)
+    g = np.array([1e-6, -1e-4, 1e-2, -1.0, 0.0], np.float32)
+    x = np.ones(5, np.float32)
+    opt.lr = np.float32(3e-3 * 0.75)
+    opt.step(x, g)
+    g64 = g.astype(np.float64)
+    want = 1.0 - 3e-3 * 0.75 * np.sqrt(1 - 0.999) / (1 - 0.9) * (0.1 * g64) / (np.sqrt(0.001 * g64 * g64) + 1e-5)
+    np.testing.assert_allclose(x, want, rtol=0, atol=2e-7)
+    assert opt.b1p == np.float32(np.float32(0.9) * np.float32(0.9)) and opt.t == 1
+    y = np.ones(5, np.float32)
+    ref = pn.AdamTF1(5, lr=3e-3 * 0.75)                            # eps 1e-8 moves the small gradients further
+    ref.step(y, g)
+    assert abs(y[0] - x[0]) > 1e-4
