@@ -1,5 +1,6 @@
 /* reacher_student_mlp.h -- C ABI of the reference's own MLP student: forward and one
- * distillation training step on a batch of rows (libreacher.so).
+ * distillation training step on a batch of rows, and its closed-loop evaluation over whole
+ * episodes (rdm_evaluate) (libreacher.so).
  *
  * Graph: student_mlp_graph (reference src/distilation/student_nn.py:51-57)
  *     x[16] -> dense 24, tanh -> dense 128, tanh -> dense 128 -> dense 32, tanh -> dense 4
@@ -73,6 +74,56 @@ int rdm_bind_grad_buffer(rdm_trainer* t, float* grad);
 int rdm_get_counter(rdm_trainer* t, int64_t* opt_steps);
 /* last `count` optimiser steps, oldest first: [count][4] = loss, sq err, rows, 0 */
 int rdm_read_metrics(rdm_trainer* t, int64_t count, double* out);
+
+/* The teacher of rdm_evaluate: the 2x64 MlpPolicy with its observation filter, same arguments as
+ * rdd_set_teacher (device pointers: params [rdd_param_count()], ob_mean [11], ob_std [11]).  The
+ * handle keeps its own copy of the net, from which every evaluation launch packs the LDS image
+ * rdd_forward's kernel packs (the same function). */
+int rdm_set_teacher(rdm_trainer* t, const float* params, const float* ob_mean, const float* ob_std);
+
+/* Whole-episode evaluation of the reference student in one launch: n_envs evaluation envs (their
+ * own states, kept in registers; no trainer's envs exist or are touched) run `episodes` consecutive
+ * 50-step episodes, stepped with the student's unclipped mean.  It is the driver's phase-2 loop
+ * (mlp_train.train(student="mlp"), reference mlp_train.py:143-204) without the optimiser steps.
+ * Episode e of env i starts from reset draw draws[(e n_envs + i) 6 ..] (the table layout of
+ * rd_set_reset_mode) or, with draws NULL, from Philox(seed, env_base + i, first_episode + e).
+ * Step s = 0..49 of an episode, per env:
+ *   ob_s  = observe(state)
+ *   T_s   = the teacher's mean[2] | logstd[2] on ob_s (rdd_forward's teacher output)
+ *   row_s = ob_s[11] | prevT[4] | prevR[1]   (the x row of rdm_forward):
+ *           s = 0: prevT = 0 and prevR = 0;
+ *           s > 0: prevT = T_{s-1}, prevR = the reward FIELD of record s-1 (below), i.e. the
+ *           reward returned by step s-2 of this episode, and for s = 1 the reward carried over
+ *           the reset: the one the previous episode's last step returned (0 in the call's first
+ *           episode).  Consecutive episodes of one env are therefore not independent.
+ *   S_s   = student(row_s) = mean[2] | logstd[2], dropout off (rdm_forward)
+ *   reward r_s = env.step(S_s[0..1])
+ * Same arithmetic as the stepwise path: the outputs are bitwise those of rd_reset, then 50 x
+ * { rdd_forward (teacher) on the observation, rdm_forward on the assembled row, rd_step with the
+ * student's mean }, for every block size and grid.
+ * Outputs (device, caller-owned; final_dist and records may be NULL):
+ *   returns    [episodes][n_envs]  r_0 + ... + r_49, f32, summed in step order
+ *   final_dist [episodes][n_envs]  |fingertip - target| after the episode's last step
+ *   records    [episodes][n_envs][50][21]  one record per step in the dataset's layout
+ *              ob[11] | reward | t_pdflat[4] | s_pdflat[4] | stepped_with:
+ *              ob = ob_s; reward = the one this env's PREVIOUS step of this call returned (0 for
+ *              episode 0 step 0; for a later episode's step 0 the previous episode's r_49, carried
+ *              over the reset); t_pdflat = T_s; s_pdflat = S_s; stepped_with = 1.
+ * No side effects on the trainer (parameters, Adam state and counter, gradient, metrics).
+ * Asynchronous on the handle's stream, no host sync, no allocation, no workspace: capturable.
+ * RD_EINVAL: NULL trainer, config or returns; n_envs < 1 (or > 2^31); episodes < 1; negative
+ * env_base, first_episode or grid (all checked before any device call and before the handle is
+ * read); no teacher set. */
+typedef struct {
+    int64_t n_envs;          /* evaluation envs (their own states)                          */
+    int64_t env_base;        /* global id of evaluation env 0 (Philox key)                  */
+    uint64_t seed;           /* Philox reset seed                                           */
+    int32_t episodes;        /* E >= 1 consecutive episodes per env                         */
+    int32_t first_episode;   /* Philox episode index of the first one                       */
+    int32_t grid;            /* workgroups; 0 = the trainer's (rdm_config.grid, one per CU)  */
+    const float* draws;      /* NULL: Philox; else device table [E][n_envs][6] (q0 q1 v0 v1 tx ty) */
+} rdm_eval_config;
+int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // distill.hip, part 5 of 5: the kernels beside the training step -- rdd_reset's and
 // rdd_set_env_state's (reset_state_kernel, check_state_kernel, init_ctl_kernel), the policy query
-// (forward_kernel) and the whole-episode evaluation (EvalArgs, tip_distance, evaluate_kernel).
+// (forward_kernel) and the whole-episode evaluation (EvalArgs, evaluate_kernel).
 // Expects distill_layout.h, distill_forward.h, rd_device.h and rd_physics.h.
 #pragma once
 
@@ -113,12 +113,6 @@ struct EvalArgs {
     int student, episodes, first_episode, gs;
 };
 
-// |fingertip - target| of the held kinematics, as rd::env_step's reward term computes it
-__device__ __forceinline__ float tip_distance(const rd::State& st) {
-    FP_SOURCE_ROUNDING();
-    return __builtin_amdgcn_sqrtf(st.dx * st.dx + st.dy * st.dy);
-}
-
 // f32 instance: <= 128 VGPRs, so that the two workgroups a CU's LDS holds are resident (4 waves
 // per SIMD: one wave's physics issues beside another's MFMAs); the bf16 instance would spill there
 template <bool BS>
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(EBLOCK, BS ? 2 : 4) void evaluate_kernel(EvalArgs a
             }
             if (valid) {
                 a.returns[(int64_t)e * n + i] = ret;
-                if (a.final_dist) a.final_dist[(int64_t)e * n + i] = tip_distance(st);
+                if (a.final_dist) a.final_dist[(int64_t)e * n + i] = rd::tip_distance(st);
             }
         }
     }

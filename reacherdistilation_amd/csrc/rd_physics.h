@@ -228,6 +228,12 @@ __device__ __forceinline__ float env_step(State& st, float a0, float a1) {
     return r;
 }
 
+// |fingertip - target| of the held kinematics, as env_step's reward term computes it
+__device__ __forceinline__ float tip_distance(const State& st) {
+    FP_SOURCE_ROUNDING();
+    return __builtin_amdgcn_sqrtf(st.dx * st.dx + st.dy * st.dy);
+}
+
 // reset_model + set_state + sim.forward(): kinematics fresh at the reset position.
 __device__ __forceinline__ void env_reset(State& st, const float* d /*q0 q1 v0 v1 tx ty*/) {
     FP_SOURCE_ROUNDING();

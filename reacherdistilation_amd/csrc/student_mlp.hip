@@ -19,6 +19,7 @@
 //    sums.  One workspace row per workgroup, summed in a fixed order by the Adam kernel
 //    (deterministic, no atomics);
 //  * exact f32 products (f32-input MFMA); tanh = 1 - 2 / (2^(2 log2(e) z) + 1).
+// The closed-loop evaluation over whole episodes (rdm_evaluate) is in student_mlp_eval.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -423,6 +424,9 @@ __global__ __launch_bounds__(BLOCK) void student_mlp_kernel(SmArgs a) {
     }
 }
 
+// the whole-episode evaluation (rdm_evaluate): tch::, SmEvalArgs, student_mlp_evaluate_kernel
+#include "student_mlp_eval.h"
+
 // flat parameter index -> (layer, k, c) -> positions in the gradient workspace and images
 struct PIdx {
     int g;        // workspace (gradient) index
@@ -552,6 +556,8 @@ struct rdm_trainer {
     float* ws = nullptr;        // [grid][WS_ROW]
     float* hist = nullptr;      // [metrics_len][4]
     uint32_t* ctl = nullptr;    // [8]
+    float* tnet = nullptr;      // rdm_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
+    bool has_teacher = false;
 };
 
 namespace {
@@ -563,6 +569,17 @@ namespace {
 // workgroups the 64-row kernel wins (4,096 rows: 51.2 vs 42.4 us).
 bool use_small_rows(int64_t n, int grid) {
     return (n + 15) / 16 <= grid / 2;
+}
+
+// rdm_evaluate's block of envs, by the same reasoning: a step is a latency chain (physics, five
+// layers, six barriers), so 16-env blocks over four times the workgroups are faster while every
+// block has a CU of its own.  No partial rows are written here, so the rule holds up to one block
+// per workgroup of the grid, not half of them (scripts/bench_evaluate_student_mlp.py,
+// profiles/evaluate_student_mlp_fused_vs_stepwise.json "fused_by_block_size", one episode: 4,096
+// envs 341 us with 16-env blocks vs 577 us with 64-env blocks; 8,192 envs, two 16-env blocks per
+// CU, 673 vs 578 us).
+bool eval_small_rows(int64_t n, int grid) {
+    return (n + 15) / 16 <= grid;
 }
 
 int launch_train(rdm_trainer* t, const float* x, const float* tgt, int64_t n, int64_t n_global) {
@@ -652,6 +669,7 @@ int rdm_create(rdm_trainer** out, const rdm_config* cfg, int device, void* hip_s
     alloc((void**)&t->ws, sizeof(float) * (size_t)t->grid * WS_ROW);
     alloc((void**)&t->hist, sizeof(float) * (size_t)t->cfg.metrics_len * N_MET);
     alloc((void**)&t->ctl, sizeof(uint32_t) * 8);
+    alloc((void**)&t->tnet, sizeof(float) * (tch::P_TOT + 2 * tch::OBD));
     t->grad = t->own_grad;
     if (e != hipSuccess) {
         rdm_destroy(t);
@@ -669,7 +687,7 @@ int rdm_destroy(rdm_trainer* t) {
     if (!t) return RD_OK;
     rd::DeviceGuard dg(t->device);
     for (void* p : {(void*)t->params, (void*)t->img, (void*)t->m, (void*)t->v, (void*)t->own_grad, (void*)t->ws,
-                    (void*)t->hist, (void*)t->ctl})
+                    (void*)t->hist, (void*)t->ctl, (void*)t->tnet})
         if (p) (void)hipFree(p);
     delete t;
     return RD_OK;
@@ -803,6 +821,56 @@ int rdm_read_metrics(rdm_trainer* t, int64_t count, double* out) {
         for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
     }
     delete[] host;
+    return RD_OK;
+}
+
+int rdm_set_teacher(rdm_trainer* t, const float* params, const float* ob_mean, const float* ob_std) {
+    if (!t || !params || !ob_mean || !ob_std) return rd::set_error(RD_EINVAL, "rdm_set_teacher: null argument");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet, params, sizeof(float) * tch::P_TOT, hipMemcpyDeviceToDevice, t->stream),
+           "rdm_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT, ob_mean, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice, t->stream),
+           "rdm_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT + tch::OBD, ob_std, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice,
+                          t->stream), "rdm_set_teacher");
+    t->has_teacher = true;
+    return RD_OK;
+}
+
+int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records) {
+    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "rdm_evaluate: null trainer, config or returns");
+    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
+        return rd::set_error(RD_EINVAL, "rdm_evaluate: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
+    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "rdm_evaluate: episodes %d < 1", cfg->episodes);
+    if (cfg->env_base < 0 || cfg->first_episode < 0 || cfg->grid < 0)
+        return rd::set_error(RD_EINVAL, "rdm_evaluate: negative env_base, first_episode or grid");
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "rdm_evaluate: no teacher set (rdm_set_teacher)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_evaluate");
+    SmEvalArgs a;
+    a.n = cfg->n_envs;
+    a.env_base = cfg->env_base;
+    a.seed = cfg->seed;
+    a.tnet = t->tnet;
+    a.img = t->img;
+    a.draws = cfg->draws;
+    a.returns = returns;
+    a.final_dist = final_dist;
+    a.records = records;
+    a.episodes = cfg->episodes;
+    a.first_episode = cfg->first_episode;
+    // a block of envs per workgroup for the whole launch, sized as rdm_forward sizes its row block
+    const int cap = cfg->grid > 0 ? cfg->grid : t->grid;
+    const bool small = eval_small_rows(a.n, cap);
+    const int rows = small ? 16 : 64;
+    const int64_t nblk = (a.n + rows - 1) / rows;
+    const int grid = (int)(nblk < cap ? nblk : cap);
+    if (small)
+        hipLaunchKernelGGL(student_mlp_evaluate_kernel<16>, dim3(grid), dim3(ELay<16>::THREADS), 0, t->stream, a);
+    else
+        hipLaunchKernelGGL(student_mlp_evaluate_kernel<64>, dim3(grid), dim3(ELay<64>::THREADS), 0, t->stream, a);
+    RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
     return RD_OK;
 }
 

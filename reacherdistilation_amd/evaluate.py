@@ -1,6 +1,10 @@
 """Whole-episode policy evaluation and episode collection in one fused launch (rdd_evaluate,
-include/reacher_distill.h; DistillTrainer.evaluate).
+include/reacher_distill.h, DistillTrainer.evaluate; rdm_evaluate, include/reacher_student_mlp.h,
+StudentMlpTrainer.evaluate).
 
+  evaluate_student_mlp  evaluate_policy for the reference's own MLP student (student_mlp_graph on
+                    rows ob | prev pdflat | prev reward): the average-reward quantity the reference
+                    plots per keep_prob, on the student it actually distils
   evaluate_policy   the fused counterpart of teacher.episode_returns: the 50-step returns of a
                     policy's mean action, what the reference reads offline from recorded episodes
                     (extract_reward.py, plot.py)
@@ -22,8 +26,9 @@ from .distill import DistillConfig, DistillTrainer
 from .env import gym_reset_draws
 from .pages import PageStore
 from .policy import MlpPolicyParams, TeacherAgent
+from .student_mlp import StudentMlpConfig, StudentMlpTrainer
 
-__all__ = ["evaluate_policy", "collect_episodes", "gym_draw_table"]
+__all__ = ["evaluate_policy", "evaluate_student_mlp", "collect_episodes", "gym_draw_table"]
 
 # collect_episodes: episodes (rounds x envs) per launch; their records (4,200 B each) are one tensor
 CHUNK_EPISODES = 16384
@@ -58,6 +63,38 @@ def evaluate_policy(params: MlpPolicyParams, episodes: int, *, n_envs: int | Non
         return ret.reshape(-1)[:episodes].cpu().numpy()
     finally:
         tr.close()
+
+
+def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, episodes: int, *,
+                         n_envs: int | None = None, seed: int = 0, reset: str = "gym", device="cuda:0") -> np.ndarray:
+    """evaluate_policy for the reference student: the 50-step returns of its mean action over
+    ``episodes`` student-stepped episodes, in one launch (StudentMlpTrainer.evaluate).
+    ``trainer_or_params`` is a StudentMlpTrainer (evaluated as it stands, on its device; ``teacher``
+    replaces its teacher unless None) or a flat parameter vector [24,380] (a trainer is made on
+    ``device`` and closed).  The teacher labels every observation: the student's row carries the
+    teacher's previous pdflat and the previous record's reward, which is carried over resets, so an
+    env's consecutive episodes (n_envs < episodes) are not independent -- as in the driver's loop.
+    Returns a float32 array [episodes] in (round, env) order; ``n_envs`` (default: one env per
+    episode), ``seed`` and ``reset`` as evaluate_policy."""
+    if reset not in ("gym", "philox"):
+        raise ValueError(f"unknown reset mode {reset!r}")
+    episodes = int(episodes)
+    n = episodes if n_envs is None else int(n_envs)
+    if episodes < 1 or n < 1:
+        raise ValueError("episodes >= 1 and n_envs >= 1")
+    E = -(-episodes // n)
+    own = not isinstance(trainer_or_params, StudentMlpTrainer)
+    tr = StudentMlpTrainer(StudentMlpConfig(seed=seed), device=device, params=trainer_or_params) if own \
+        else trainer_or_params
+    try:
+        if teacher is not None:
+            tr.set_teacher(teacher)
+        draws = gym_draw_table(seed, n, E) if reset == "gym" else None
+        ret = tr.evaluate(n, E, seed=seed, draws=draws).returns
+        return ret.reshape(-1)[:episodes].cpu().numpy()
+    finally:
+        if own:
+            tr.close()
 
 
 def collect_episodes(episodes: int, n_envs: int = 1, *, seed: int = 0, teacher: MlpPolicyParams | None = None,

@@ -21,6 +21,7 @@ import torch
 from . import _native as nat
 from .config import OBSPACE_SHAPE, PDFLAT_SHAPE
 from .dist import allreduce_sum_
+from .distill import EvalResult
 
 P = nat.P
 I32, I64, U64, F32, INT = nat.I32, nat.I64, nat.U64, nat.F32, nat.INT
@@ -36,7 +37,14 @@ class RdmConfig(ctypes.Structure):
                 ("metrics_len", I32), ("keep_prob", F32), ("seed", U64), ("row_base", I64)]
 
 
+class RdmEvalConfig(ctypes.Structure):
+    _fields_ = [("n_envs", I64), ("env_base", I64), ("seed", U64), ("episodes", I32), ("first_episode", I32),
+                ("grid", I32), ("draws", P)]
+
+
 nat.register({
+    "rdm_set_teacher": (INT, [P, P, P, P]),
+    "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
     "rdm_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdmConfig), INT, P]),
     "rdm_destroy": (INT, [P]),
@@ -104,6 +112,7 @@ class StudentMlpTrainer:
             nat.check(self._lib.rdm_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
                                            nat.stream_handle(self.device)), "rdm_create")
         self._h = h
+        self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._grad = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdm_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdm_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed) if params is None else params)
@@ -141,6 +150,15 @@ class StudentMlpTrainer:
         nat.check(self._lib.rdm_get_params(self._h, nat.ptr(out)), "rdm_get_params")
         return out
 
+    def set_teacher(self, p):
+        """The teacher of evaluate(): an MlpPolicyParams (the 2x64 MlpPolicy with its observation
+        filter), as DistillTrainer.set_teacher takes it."""
+        f, mu, sd = p.device_tensors(self.device)
+        self._sync_stream()
+        nat.check(self._lib.rdm_set_teacher(self._h, nat.ptr(f), nat.ptr(mu), nat.ptr(sd)), "rdm_set_teacher")
+        torch.cuda.current_stream(self.device).synchronize()
+        self.teacher = p
+
     def reset_optimizer(self):
         self._sync_stream()
         nat.check(self._lib.rdm_reset(self._h), "rdm_reset")
@@ -159,6 +177,46 @@ class StudentMlpTrainer:
         self._sync_stream()
         nat.check(self._lib.rdm_forward(self._h, nat.ptr(x), x.shape[0], nat.ptr(out)), "rdm_forward")
         return out
+
+    def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
+                 first_episode: int = 0, draws=None, final_dist: bool = False, records: bool = False,
+                 grid: int = 0) -> EvalResult:
+        """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
+        with this student's mean action in ONE launch (rdm_evaluate): the phase-2 loop of
+        mlp_train.train(student="mlp") without the optimiser steps.  Per step the teacher set by
+        set_teacher() labels the observation, the student sees the row ob | the teacher's previous
+        pdflat | the previous record's reward (zeros at an episode's first step; the reward is
+        carried over resets, DeviceDataset.current_prev), and its unclipped mean steps the env.
+        Bitwise the stepwise loop -- BatchedReacher.reset(), then 50 x {DistillTrainer.forward
+        (teacher), rows(), forward(), BatchedReacher.step(mean)} per episode -- with no side effect
+        on the trainer.  Episode e of env i resets from ``draws[e, i]`` ([E, n_envs, 6]: q0 q1 v0 v1
+        tx ty) or, without a table, from Philox(seed, env_base + i, first_episode + e).  Returns a
+        distill.EvalResult: returns [E, n]; final_dist [E, n]; records [E, n, 50, 21] in the dataset's
+        layout (both pdflats, stepped_with = 1), so that records.view(E * n, 50, 21) goes into
+        DeviceDataset.write_episodes.  Asynchronous on the current stream; no workspace: capturable."""
+        n, E = int(n_envs), int(episodes)
+        if n < 1 or E < 1:
+            raise ValueError("n_envs >= 1 and episodes >= 1")
+        if self.teacher is None:
+            raise RuntimeError("evaluate() needs a teacher: call set_teacher(MlpPolicyParams) first")
+        table = None
+        if draws is not None:
+            table = torch.as_tensor(draws).to(self.device, torch.float32).contiguous()
+            if table.shape != (E, n, 6):
+                raise ValueError(f"draws must be [{E}, {n}, 6]")
+        kw = dict(dtype=torch.float32, device=self.device)
+        res = EvalResult(torch.empty(E, n, **kw),
+                         torch.empty(E, n, **kw) if final_dist else None,
+                         torch.empty(E, n, 50, 21, **kw) if records else None)
+        c = RdmEvalConfig(n_envs=n, env_base=int(env_base), seed=int(seed) % 2 ** 64, episodes=E,
+                          first_episode=int(first_episode), grid=int(grid),
+                          draws=table.data_ptr() if table is not None else None)
+        self._sync_stream()
+        nat.check(self._lib.rdm_evaluate(self._h, ctypes.byref(c), nat.ptr(res.returns),
+                                         nat.ptr(res.final_dist) if final_dist else None,
+                                         nat.ptr(res.records) if records else None), "rdm_evaluate")
+        self._keep_eval = table   # the launch reads it asynchronously
+        return res
 
     def rollout(self, x, t_pdflat, n_global: int | None = None) -> torch.Tensor:
         """Gradient of this rank's rows into grad(); returns the gradient tensor."""
