@@ -114,6 +114,57 @@ int rdl_head_path(const rdl_trainer* t);
 /* [count][4] = loss, sum |mu_s - mu_t|^2, rows (T x B), 0 */
 int rdl_read_metrics(rdl_trainer* t, int64_t count, double* out);
 
+/* The teacher of rdl_evaluate: the 2x64 MlpPolicy with its observation filter, same arguments as
+ * rdd_set_teacher / rdm_set_teacher (device pointers: params [rdd_param_count()], ob_mean [11],
+ * ob_std [11]).  The handle keeps its own copy of the net, from which every evaluation launch
+ * packs the LDS image rdd_forward's kernel packs (the same function). */
+int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, const float* ob_std);
+
+/* Whole-episode evaluation of the LSTM student in one rollout launch: n_envs evaluation envs (their
+ * own states; no trainer's envs exist or are touched) run `episodes` consecutive 50-step episodes,
+ * stepped with the student's unclipped mean.  It is the query loop of lstm_train.train (reference
+ * lstm_train.py:163-204) without the optimiser steps, one env being column B-1 of the driver's
+ * query batch.  Episode e of env i starts from reset draw draws[(e n_envs + i) 6 ..] or, with draws
+ * NULL, from Philox(seed, env_base + i, first_episode + e) (as rdm_evaluate).  With T =
+ * rdl_config.steps, step s = 0..49 of an episode, per env:
+ *   ob_s = observe(state)
+ *   T_s  = the teacher's mean[2] | logstd[2] on ob_s (rdd_forward's teacher output)
+ *   window: position p = 0..T-1 holds record j = s - (T-1) + p of this episode:
+ *           j >= 0: ob_j[11] | prev = T_{j-1} (0 at j = 0);  j < 0: ob = 0, prev = 0
+ *   S_s  = pdflat of unrolled position T-1 (head T-1) of rdl_forward on that window, dropout off,
+ *          from the final (c, h) of this env's previous query: carried over episode boundaries,
+ *          state0 (zeros when NULL) at the call's first step
+ *   reward r_s = env.step(S_s[0..1])
+ * Same arithmetic as the stepwise path: the outputs are bitwise those of rd_reset, then 50 x
+ * { rdd_forward (teacher), rdl_forward on the windows, rd_step with the student's mean }, for every
+ * grid.  T is at most RDL_EVAL_MAX_STEPS, the records of history the kernel keeps on chip per env.
+ * Outputs (device, caller-owned; final_dist, records and state_out may be NULL):
+ *   returns    [episodes][n_envs]  r_0 + ... + r_49, f32, summed in step order
+ *   final_dist [episodes][n_envs]  |fingertip - target| after the episode's last step
+ *   records    [episodes][n_envs][50][21]  ob[11] | reward | t_pdflat[4] | s_pdflat[4] | stepped_with:
+ *              reward = the one this env's PREVIOUS step of this call returned (0 at the call's first
+ *              step); t_pdflat = T_s; s_pdflat = S_s; stepped_with = 1
+ *   state_out  [2][n_envs][200] = (c, h) after the call's last query; state0 has the same layout
+ * No side effects on the trainer: parameters, Adam state and counter, gradient, metrics, the
+ * activations rdl_final_state reads, the persistent kernels' barrier words and granule generation.
+ * Asynchronous on the handle's stream, no host sync, no allocation (the packed image of the cell's
+ * weights is the handle's, rebuilt on the stream by every call): capturable.
+ * RD_EINVAL: NULL trainer, config or returns; n_envs < 1 (or > 2^31); episodes < 1; negative
+ * env_base, first_episode or grid (all checked before any device call and before the handle is
+ * read); no teacher set; rdl_config.steps > RDL_EVAL_MAX_STEPS. */
+#define RDL_EVAL_MAX_STEPS 16
+typedef struct {
+    int64_t n_envs;          /* evaluation envs (their own states)                          */
+    int64_t env_base;        /* global id of evaluation env 0 (Philox key)                  */
+    uint64_t seed;           /* Philox reset seed                                           */
+    int32_t episodes;        /* E >= 1 consecutive episodes per env                         */
+    int32_t first_episode;   /* Philox episode index of the first one                       */
+    int32_t grid;            /* workgroups (16 envs each per pass); 0 = one per CU          */
+    const float* draws;      /* NULL: Philox; else device table [E][n_envs][6] (q0 q1 v0 v1 tx ty) */
+} rdl_eval_config;
+int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
+                 float* records, float* state_out);
+
 #ifdef __cplusplus
 }
 #endif

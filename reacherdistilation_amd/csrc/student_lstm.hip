@@ -709,15 +709,15 @@ __global__ __launch_bounds__(256) void lstm_bptt_persist_kernel(const float* __r
 // k order and epilogue (acc + b, tanhf) as the unsplit rd_gemm launches it replaces.
 constexpr int HF_ROWS = 16, HF_MAX_ROWS = 1 << 18;
 constexpr int64_t HPART_MAX_FLOATS = (int64_t)128 << 20;   // the fused head's partial rows: at most 512 MB (reacher_student_lstm.h)
-template <int K, int N, bool TANH, int LI, int LO>
+template <int K, int N, bool TANH, int NW = 4, int LI, int LO>
 __device__ __forceinline__ void head_layer(const float (*in)[LI], float (*out)[LO], const float* __restrict__ W,
                                            const float* __restrict__ b, float* __restrict__ gout, int ldg,
                                            int64_t row0, int64_t R) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, gq = lane >> 4;
     constexpr int NB = (N + 15) / 16;
 #pragma unroll
-    for (int it = 0; it < (NB + 3) / 4; ++it) {   // unrolled: every weight load of the layer in flight at once
-        const int cb = wave + 4 * it;
+    for (int it = 0; it < (NB + NW - 1) / NW; ++it) {   // unrolled: every weight load of the layer in flight at once
+        const int cb = wave + NW * it;   // NW waves share the layer's column blocks
         if (cb >= NB) break;
         const int col = 16 * cb + i;
         const bool cv = col < N;
@@ -1466,6 +1466,9 @@ __global__ void init_ctl_kernel(uint32_t* ctl, float b1, float b2) {
 
 constexpr int64_t SPLIT_FLOATS = 16 << 20;  // split-K partials (64 MB)
 
+// the whole-episode evaluation (rdl_evaluate): tch::, lstm_eval_pack_kernel, student_lstm_evaluate_kernel
+#include "student_lstm_eval.h"
+
 }  // namespace
 
 struct rdl_trainer {
@@ -1492,6 +1495,9 @@ struct rdl_trainer {
     unsigned long long* hx = nullptr;      // persistent forward: per-step-parity h granules
     float* qbuf = nullptr;     // persistent BPTT: Q = prev^T dz [4][800]
     int64_t last_B = 0;   // windows of the last forward pass (rdl_final_state)
+    float* tnet = nullptr;     // rdl_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
+    float* eimg = nullptr;     // rdl_evaluate's packed image of Wl [EV_IMG], rebuilt by every call
+    bool has_teacher = false;
 };
 
 namespace {
@@ -1847,6 +1853,8 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
     if (e == hipSuccess) e = hipMalloc((void**)&t->hx, sizeof(unsigned long long) * 2 * PR_ROWS * U);
     if (e == hipSuccess) e = hipMemsetAsync(t->hx, 0, sizeof(unsigned long long) * 2 * PR_ROWS * U, t->stream);
     alloc(&t->qbuf, 4 * G4);
+    alloc(&t->tnet, tch::P_TOT + 2 * tch::OBD);
+    alloc(&t->eimg, EV_IMG);
     if (e == hipSuccess) e = hipMemsetAsync(t->bar, 0, sizeof(uint32_t) * 4, t->stream);
     t->grad = t->own_grad;
     if (e != hipSuccess) {
@@ -1877,7 +1885,7 @@ int rdl_destroy(rdl_trainer* t) {
     rd::DeviceGuard dg(t->device);
     float* bufs[] = {t->params, t->m, t->v, t->own_grad, t->X, t->H, t->Cs, t->Z, t->G, t->A1, t->A2, t->A3, t->A4,
                      t->Y, t->dY, t->D32, t->D64a, t->D128, t->D64b, t->dHh, t->dP, t->dhn, t->dc, t->split,
-                     t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack};
+                     t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack, t->tnet, t->eimg};
     for (float* p : bufs)
         if (p) (void)hipFree(p);
     if (t->hx) (void)hipFree(t->hx);
@@ -2039,6 +2047,61 @@ int rdl_read_metrics(rdl_trainer* t, int64_t count, double* out) {
         for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
     }
     delete[] host;
+    return RD_OK;
+}
+
+int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, const float* ob_std) {
+    if (!t || !params || !ob_mean || !ob_std) return rd::set_error(RD_EINVAL, "rdl_set_teacher: null argument");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet, params, sizeof(float) * tch::P_TOT, hipMemcpyDeviceToDevice, t->stream),
+           "rdl_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT, ob_mean, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice, t->stream),
+           "rdl_set_teacher");
+    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT + tch::OBD, ob_std, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice,
+                          t->stream), "rdl_set_teacher");
+    t->has_teacher = true;
+    return RD_OK;
+}
+
+int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
+                 float* records, float* state_out) {
+    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "rdl_evaluate: null trainer, config or returns");
+    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
+        return rd::set_error(RD_EINVAL, "rdl_evaluate: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
+    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "rdl_evaluate: episodes %d < 1", cfg->episodes);
+    if (cfg->env_base < 0 || cfg->first_episode < 0 || cfg->grid < 0)
+        return rd::set_error(RD_EINVAL, "rdl_evaluate: negative env_base, first_episode or grid");
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "rdl_evaluate: no teacher set (rdl_set_teacher)");
+    if (t->T > EV_MAX_T)
+        return rd::set_error(RD_EINVAL, "rdl_evaluate: %d unrolled steps, the kernel keeps at most %d records of history",
+                             t->T, EV_MAX_T);
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_evaluate");
+    hipLaunchKernelGGL(lstm_eval_pack_kernel, dim3((EV_IMG + 255) / 256), dim3(256), 0, t->stream,
+                       (const float*)t->params, t->eimg);
+    RD_HIP(hipGetLastError(), "lstm_eval_pack_kernel launch");
+    LsEvalArgs a;
+    a.n = cfg->n_envs;
+    a.env_base = cfg->env_base;
+    a.seed = cfg->seed;
+    a.tnet = t->tnet;
+    a.P = t->params;
+    a.img = t->eimg;
+    a.draws = cfg->draws;
+    a.state0 = state0;
+    a.returns = returns;
+    a.final_dist = final_dist;
+    a.records = records;
+    a.state_out = state_out;
+    a.episodes = cfg->episodes;
+    a.first_episode = cfg->first_episode;
+    a.T = t->T;
+    // a block of 16 envs per workgroup for the whole launch, one workgroup per CU (its LDS)
+    const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = cfg->grid > 0 ? cfg->grid : t->cus;
+    hipLaunchKernelGGL(student_lstm_evaluate_kernel, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0,
+                       t->stream, a);
+    RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
     return RD_OK;
 }
 

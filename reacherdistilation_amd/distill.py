@@ -49,6 +49,7 @@ class EvalResult:
     returns: torch.Tensor                      # [E, n] f32: each episode's 50 step rewards summed in step order
     final_dist: torch.Tensor | None = None     # [E, n] f32: |fingertip - target| after the episode's last step
     records: torch.Tensor | None = None        # [E, n, 50, 21] f32 in dataset.py's record layout
+    state: torch.Tensor | None = None          # StudentLstmTrainer.evaluate(final_state=True): [2, n, 200] = (c, h)
 
 
 nat.register({

@@ -1,7 +1,11 @@
 """Whole-episode policy evaluation and episode collection in one fused launch (rdd_evaluate,
 include/reacher_distill.h, DistillTrainer.evaluate; rdm_evaluate, include/reacher_student_mlp.h,
-StudentMlpTrainer.evaluate).
+StudentMlpTrainer.evaluate; rdl_evaluate, include/reacher_student_lstm.h,
+StudentLstmTrainer.evaluate).
 
+  evaluate_student_lstm  the same for the reference's LSTM student (student_lstm_graph on the window
+                    of the episode's last T records, the LSTM state carried from query to query),
+                    the student lstm_train.py distils; its weights stream from L2
   evaluate_student_mlp  evaluate_policy for the reference's own MLP student (student_mlp_graph on
                     rows ob | prev pdflat | prev reward): the average-reward quantity the reference
                     plots per keep_prob, on the student it actually distils
@@ -11,24 +15,25 @@ StudentMlpTrainer.evaluate).
   collect_episodes  teacher.collect_reward's signature and result (the same dataset, bit for bit)
                     with one launch per chunk of rounds in place of 100 launches per round
 
-Both keep each env's whole episode in registers and the weights in LDS (DESIGN.md §3
+All keep each env's whole episode on chip, the 2x64 nets' weights in LDS (DESIGN.md §3
 "Evaluation"); the arithmetic is that of the stepwise loops they replace, so the results are
-bitwise theirs (tests/test_evaluate_gpu.py).
+bitwise theirs (tests/test_evaluate_gpu.py, tests/test_student_*_evaluate_gpu.py).
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from .config import MAX_CAPACITY
+from .config import MAX_CAPACITY, STEPS_UNROLLED
 from .dataset import DeviceDataset
 from .distill import DistillConfig, DistillTrainer
 from .env import gym_reset_draws
 from .pages import PageStore
 from .policy import MlpPolicyParams, TeacherAgent
+from .student_lstm import StudentLstmConfig, StudentLstmTrainer
 from .student_mlp import StudentMlpConfig, StudentMlpTrainer
 
-__all__ = ["evaluate_policy", "evaluate_student_mlp", "collect_episodes", "gym_draw_table"]
+__all__ = ["evaluate_policy", "evaluate_student_mlp", "evaluate_student_lstm", "collect_episodes", "gym_draw_table"]
 
 # collect_episodes: episodes (rounds x envs) per launch; their records (4,200 B each) are one tensor
 CHUNK_EPISODES = 16384
@@ -86,6 +91,39 @@ def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, epi
     own = not isinstance(trainer_or_params, StudentMlpTrainer)
     tr = StudentMlpTrainer(StudentMlpConfig(seed=seed), device=device, params=trainer_or_params) if own \
         else trainer_or_params
+    try:
+        if teacher is not None:
+            tr.set_teacher(teacher)
+        draws = gym_draw_table(seed, n, E) if reset == "gym" else None
+        ret = tr.evaluate(n, E, seed=seed, draws=draws).returns
+        return ret.reshape(-1)[:episodes].cpu().numpy()
+    finally:
+        if own:
+            tr.close()
+
+
+def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, episodes: int, *,
+                          n_envs: int | None = None, seed: int = 0, reset: str = "gym", device="cuda:0",
+                          steps: int = STEPS_UNROLLED) -> np.ndarray:
+    """evaluate_student_mlp for the reference's LSTM student: the 50-step returns of its mean action
+    over ``episodes`` student-stepped episodes, in one rollout launch (StudentLstmTrainer.evaluate).
+    ``trainer_or_params`` is a StudentLstmTrainer (evaluated as it stands, on its device; ``teacher``
+    replaces its teacher unless None) or a flat parameter vector of student_lstm.n_params(steps)
+    floats (a trainer of ``steps`` unrolled steps is made on ``device`` and closed).  The LSTM state
+    starts at zero and is carried from query to query over the resets, as the driver carries it, so
+    an env's consecutive episodes (n_envs < episodes) are not independent.  Returns a float32 array
+    [episodes] in (round, env) order; ``n_envs`` (default: one env per episode), ``seed`` and
+    ``reset`` as evaluate_policy."""
+    if reset not in ("gym", "philox"):
+        raise ValueError(f"unknown reset mode {reset!r}")
+    episodes = int(episodes)
+    n = episodes if n_envs is None else int(n_envs)
+    if episodes < 1 or n < 1:
+        raise ValueError("episodes >= 1 and n_envs >= 1")
+    E = -(-episodes // n)
+    own = not isinstance(trainer_or_params, StudentLstmTrainer)
+    tr = StudentLstmTrainer(StudentLstmConfig(seed=seed, steps=int(steps)), device=device,
+                            params=trainer_or_params) if own else trainer_or_params
     try:
         if teacher is not None:
             tr.set_teacher(teacher)

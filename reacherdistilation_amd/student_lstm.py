@@ -23,6 +23,7 @@ import torch
 from . import _native as nat
 from .config import LSTM_BATCH_SIZE, NUM_UNITS, OBSPACE_SHAPE, PDFLAT_SHAPE, STEPS_UNROLLED
 from .dist import allreduce_sum_
+from .distill import EvalResult
 
 P = nat.P
 I32, I64, U64, F32, INT = nat.I32, nat.I64, nat.U64, nat.F32, nat.INT
@@ -55,7 +56,14 @@ class RdlConfig(ctypes.Structure):
                 ("kernels", I32)]
 
 
+class RdlEvalConfig(ctypes.Structure):
+    _fields_ = [("n_envs", I64), ("env_base", I64), ("seed", U64), ("episodes", I32), ("first_episode", I32),
+                ("grid", I32), ("draws", P)]
+
+
 nat.register({
+    "rdl_set_teacher": (INT, [P, P, P, P]),
+    "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
     "rdl_param_count": (I64, [I32]),
     "rdl_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdlConfig), INT, P]),
     "rdl_destroy": (INT, [P]),
@@ -130,6 +138,7 @@ class StudentLstmTrainer:
             nat.check(self._lib.rdl_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
                                            nat.stream_handle(self.device)), "rdl_create")
         self._h = h
+        self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -157,6 +166,15 @@ class StudentLstmTrainer:
         self._sync_stream()
         nat.check(self._lib.rdl_set_params(self._h, nat.ptr(p)), "rdl_set_params")
         torch.cuda.current_stream(self.device).synchronize()
+
+    def set_teacher(self, p):
+        """The teacher of evaluate(): an MlpPolicyParams (the 2x64 MlpPolicy with its observation
+        filter), as DistillTrainer.set_teacher takes it."""
+        f, mu, sd = p.device_tensors(self.device)
+        self._sync_stream()
+        nat.check(self._lib.rdl_set_teacher(self._h, nat.ptr(f), nat.ptr(mu), nat.ptr(sd)), "rdl_set_teacher")
+        torch.cuda.current_stream(self.device).synchronize()
+        self.teacher = p
 
     @property
     def fused_head(self) -> bool:
@@ -260,6 +278,54 @@ class StudentLstmTrainer:
         nat.check(self._lib.rdl_forward(self._h, nat.ptr(ob), nat.ptr(prev), nat.ptr(st) if st is not None else None,
                                         B, nat.ptr(out), nat.ptr(fin)), "rdl_forward")
         return out, fin
+
+    def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
+                 first_episode: int = 0, draws=None, state0=None, final_dist: bool = False, records: bool = False,
+                 final_state: bool = False, grid: int = 0) -> EvalResult:
+        """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
+        with this student's mean action in ONE rollout launch (rdl_evaluate): the query loop of
+        lstm_train.train without the optimiser steps, each env being column B-1 of the driver's
+        query.  Per step the teacher set by set_teacher() labels the observation; the student sees the
+        window of the episode's last T records (ob | the teacher's previous pdflat; zero rows before
+        the episode's first), runs from the final (c, h) of the env's previous query -- carried over
+        episode boundaries, ``state0`` [2, n, 200] or zeros at the call's first step -- and the
+        unclipped mean of unrolled position T-1 steps the env.  Bitwise the stepwise loop --
+        BatchedReacher.reset(), then 50 x {DistillTrainer.forward (teacher), the windows,
+        forward(ob_w, prev_w, state)[T-1], BatchedReacher.step(mean)} per episode -- with no side
+        effect on the trainer.  Episode e of env i resets from ``draws[e, i]`` ([E, n_envs, 6]) or,
+        without a table, from Philox(seed, env_base + i, first_episode + e).  Returns a
+        distill.EvalResult: returns [E, n]; final_dist [E, n]; records [E, n, 50, 21] in the dataset's
+        layout (stepped_with = 1); state [2, n, 200] = (c, h) after the last query with
+        ``final_state``.  Asynchronous on the current stream; no allocation in the library: capturable."""
+        n, E = int(n_envs), int(episodes)
+        if n < 1 or E < 1:
+            raise ValueError("n_envs >= 1 and episodes >= 1")
+        if self.teacher is None:
+            raise RuntimeError("evaluate() needs a teacher: call set_teacher(MlpPolicyParams) first")
+        table = None
+        if draws is not None:
+            table = torch.as_tensor(draws).to(self.device, torch.float32).contiguous()
+            if table.shape != (E, n, 6):
+                raise ValueError(f"draws must be [{E}, {n}, 6]")
+        if state0 is not None:
+            state0 = torch.as_tensor(state0).to(self.device, torch.float32).contiguous()
+            if tuple(state0.shape) != (2, n, NUM_UNITS):
+                raise ValueError(f"state0 must be [2, {n}, {NUM_UNITS}]")
+        kw = dict(dtype=torch.float32, device=self.device)
+        res = EvalResult(torch.empty(E, n, **kw),
+                         torch.empty(E, n, **kw) if final_dist else None,
+                         torch.empty(E, n, 50, 21, **kw) if records else None,
+                         torch.empty(2, n, NUM_UNITS, **kw) if final_state else None)
+        c = RdlEvalConfig(n_envs=n, env_base=int(env_base), seed=int(seed) % 2 ** 64, episodes=E,
+                          first_episode=int(first_episode), grid=int(grid),
+                          draws=table.data_ptr() if table is not None else None)
+        self._sync_stream()
+        nat.check(self._lib.rdl_evaluate(self._h, ctypes.byref(c), nat.ptr(state0) if state0 is not None else None,
+                                         nat.ptr(res.returns), nat.ptr(res.final_dist) if final_dist else None,
+                                         nat.ptr(res.records) if records else None,
+                                         nat.ptr(res.state) if final_state else None), "rdl_evaluate")
+        self._keep_eval = (table, state0)   # the launch reads them asynchronously
+        return res
 
     def rollout(self, ob, prev_pdflat, t_pdflat, state0=None, windows_global: int | None = None):
         ob, prev, tgt, st, B = self._windows(ob, prev_pdflat, t_pdflat, state0)
