@@ -1,6 +1,7 @@
 /* reacher_student_mlp.h -- C ABI of the reference's own MLP student: forward and one
  * distillation training step on a batch of rows, and its closed-loop evaluation over whole
- * episodes (rdm_evaluate) (libreacher.so).
+ * episodes (rdm_evaluate), and its batched on-policy distillation over persistent envs
+ * (rdm_step_envs) (libreacher.so).
  *
  * Graph: student_mlp_graph (reference src/distilation/student_nn.py:51-57)
  *     x[16] -> dense 24, tanh -> dense 128, tanh -> dense 128 -> dense 32, tanh -> dense 4
@@ -124,6 +125,62 @@ typedef struct {
     const float* draws;      /* NULL: Philox; else device table [E][n_envs][6] (q0 q1 v0 v1 tx ty) */
 } rdm_eval_config;
 int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records);
+
+/* Batched on-policy distillation of the reference student: the handle keeps n_envs persistent envs
+ * in lockstep, and one call takes them through K env steps, labels every step with the teacher
+ * (rdm_set_teacher), and trains on the K n_envs rows: the driver's loops (mlp_train.py:120-204)
+ * over many envs, as rdd_step is for the 2x64 MlpPolicy student.
+ * Per env the device keeps the state, the clock (step 0..49 of the episode, episode), the reward
+ * its last step returned, and the previous record's fields (the teacher's pdflat, the reward field).
+ * One env step is exactly rdm_evaluate's:
+ *   ob_s  = observe(state);  T_s = the teacher's pdflat on ob_s
+ *   row_s = ob_s[11] | T_{s-1}[4] | the reward field of record s-1 (zeros at an episode's step 0;
+ *           the carried reward survives the reset and reaches step 1's row)
+ *   S_s   = student(row_s), dropout off;  r_s = env.step(mean)
+ * with mean = S_s[0..1] (RDM_ACT_STUDENT) or T_s[0..1] (RDM_ACT_TEACHER: the driver's phase 1; the
+ * student is not evaluated and s_pdflat is written as 0).  After its step 49 an env resets, inside
+ * that step as rd_step does, from Philox(seed, env_base + i, episode + 1).  The clock is on the
+ * device: no host-side count enters a launch, so a captured call replays the NEXT K steps.
+ * Outputs (device, caller-owned, step-major: row k n_envs + i is env i's k-th step of the call):
+ *   x        [K][n_envs][16]  the undropped rows (16-byte aligned, required)
+ *   t_pdflat [K][n_envs][4]   T_s (16-byte aligned, required)
+ *   s_pdflat [K][n_envs][4]   S_s, or 0 under RDM_ACT_TEACHER (may be NULL)
+ *   reward   [K][n_envs]      r_s (may be NULL)
+ * Same arithmetic as the stepwise path: the outputs are bitwise those of rd_reset, then K x
+ * { rdd_forward (teacher), rdm_forward on the assembled row, rd_step }, for every block size, grid
+ * and split of the steps over calls; rdm_step_envs leaves the parameters, gradient, metrics and
+ * counter of rdm_step on those K n_envs rows (the same two launches on (x, t_pdflat, K n_envs)), so
+ * the dropout mask of env i's k-th row is keyed (row_base + k n_envs + i, optimiser step).
+ * Asynchronous on the handle's stream; no allocation outside rdm_envs_attach: capturable.
+ * rdm_destroy frees the envs.  Multi-GPU is out of scope: there is no rank-sharded variant of these
+ * calls (a caller may still all-reduce rdm_grad_buffer() between rdm_rollout_envs and rdm_apply,
+ * but n_global is this rank's K n_envs).
+ * RD_EINVAL, naming the function and the field: NULL trainer, config, x or t_pdflat; x or t_pdflat
+ * not 16-byte aligned; n_envs < 1 (or > 2^31); steps < 1; unknown act_with; negative env_base or
+ * grid (all before any device call and before the handle is read); then, from the handle: no envs
+ * attached; steps x n_envs > 2^31; no teacher set. */
+#define RDM_ACT_TEACHER 0
+#define RDM_ACT_STUDENT 1
+typedef struct {
+    int64_t n_envs;          /* persistent envs of the handle                               */
+    int64_t env_base;        /* global id of env 0 (Philox key)                             */
+    uint64_t seed;           /* Philox reset seed                                           */
+    int32_t grid;            /* workgroups; 0 = the trainer's (rdm_config.grid, one per CU)  */
+} rdm_envs_config;
+
+/* allocate (or replace) the handle's envs, then reset them */
+int rdm_envs_attach(rdm_trainer* t, const rdm_envs_config* cfg);
+/* episode 0 of every env; clocks, carried reward and prev fields to 0 */
+int rdm_envs_reset(rdm_trainer* t);
+/* K env steps, no training, no side effect on params / Adam / grad / metrics */
+int rdm_envs_act(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward);
+/* act, then the training launch on these K n rows (n_global = K n): gradient in rdm_grad_buffer() */
+int rdm_rollout_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat,
+                     float* reward);
+/* rdm_rollout_envs + rdm_apply: one optimiser step */
+int rdm_step_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward);
+/* state [8][n_envs] SoA as rd_get_state (device); env 0's clock; host-synchronising */
+int rdm_envs_get_state(rdm_trainer* t, float* state, int32_t* step, int32_t* episode);
 
 #ifdef __cplusplus
 }

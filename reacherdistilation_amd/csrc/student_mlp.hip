@@ -19,7 +19,8 @@
 //    sums.  One workspace row per workgroup, summed in a fixed order by the Adam kernel
 //    (deterministic, no atomics);
 //  * exact f32 products (f32-input MFMA); tanh = 1 - 2 / (2^(2 log2(e) z) + 1).
-// The closed-loop evaluation over whole episodes (rdm_evaluate) is in student_mlp_eval.h.
+// The closed-loop evaluation over whole episodes (rdm_evaluate) is in student_mlp_eval.h, the
+// persistent envs of the batched on-policy step (rdm_step_envs) in student_mlp_envs.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -117,7 +118,10 @@ struct Part {
 };
 
 // Forward of layer L: Y[row][pk(c)] = act(b[c] + sum_k X[row][k] W[k][c]), c = 16 cb + i.
-template <int RB, int L, int SI, int SO>
+// FENCE: every k-group's MFMAs are SrcC-fenced (rd_device.h), for a kernel in which hipcc would
+// otherwise load the next operands into a register an in-flight MFMA still reads as SrcC (the bias
+// quad shared by a wave's row blocks: student_mlp_envs_kernel<64, true>); the same values.
+template <int RB, int L, int SI, int SO, bool FENCE = false>
 __device__ __forceinline__ void fwd_layer(const float* X, float* Y, const float* img, int wave, int i, int g) {
     constexpr int NCB = MP[L] / 16, KG = (IN[L] + 15) / 16;
     using PT = Part<NCB, RB>;
@@ -139,10 +143,12 @@ __device__ __forceinline__ void fwd_layer(const float* X, float* Y, const float*
 #pragma unroll
         for (int c = 0; c < PT::CPW; ++c) {
             const f32x4 w = ld4(W + ((S * MP[L] + 16 * PT::cb(wave, c) + i) << 4) + 4 * g);
+            if constexpr (FENCE) fence_begin(acc[c]);
 #pragma unroll
             for (int sub = 0; sub < 4; ++sub)
 #pragma unroll
                 for (int r = 0; r < PT::RPW; ++r) acc[c][r] = mfma(a[r][sub], w[sub], acc[c][r]);
+            if constexpr (FENCE) fence_end(acc[c]);
         }
     }
 #pragma unroll
@@ -426,6 +432,8 @@ __global__ __launch_bounds__(BLOCK) void student_mlp_kernel(SmArgs a) {
 
 // the whole-episode evaluation (rdm_evaluate): tch::, SmEvalArgs, student_mlp_evaluate_kernel
 #include "student_mlp_eval.h"
+// the persistent envs (rdm_envs_*, rdm_step_envs): SmEnvsArgs, student_mlp_envs_kernel
+#include "student_mlp_envs.h"
 
 // flat parameter index -> (layer, k, c) -> positions in the gradient workspace and images
 struct PIdx {
@@ -558,6 +566,13 @@ struct rdm_trainer {
     uint32_t* ctl = nullptr;    // [8]
     float* tnet = nullptr;      // rdm_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
     bool has_teacher = false;
+    // the persistent envs (rdm_envs_attach)
+    int64_t envs_n = 0, envs_base = 0;
+    uint64_t envs_seed = 0;
+    int envs_grid = 0;              // 0 = grid
+    float* env_state = nullptr;     // [8][envs_n]
+    float* env_aux = nullptr;       // [ENV_AUX][envs_n]
+    int32_t* env_clock = nullptr;   // [2][envs_n]
 };
 
 namespace {
@@ -635,6 +650,71 @@ bool bad_rows(const float* x, int64_t n) {
     return !x || n <= 0 || n > ((int64_t)1 << 31) || ((uintptr_t)x & 15) != 0;
 }
 
+SmEnvsArgs envs_args(const rdm_trainer* t) {
+    SmEnvsArgs a{};
+    a.n = t->envs_n;
+    a.env_base = t->envs_base;
+    a.seed = t->envs_seed;
+    a.tnet = t->tnet;
+    a.img = t->img;
+    a.state = t->env_state;
+    a.aux = t->env_aux;
+    a.clock = t->env_clock;
+    return a;
+}
+
+// The argument checks of rdm_envs_act / rdm_rollout_envs / rdm_step_envs, `fn` naming the caller:
+// everything that needs no handle first, then what the handle says.
+int envs_check(const char* fn, const rdm_trainer* t, int act_with, int steps, const float* x, const float* t_pdflat) {
+    if (!t) return rd::set_error(RD_EINVAL, "%s: null trainer", fn);
+    if (!x) return rd::set_error(RD_EINVAL, "%s: null x", fn);
+    if (!t_pdflat) return rd::set_error(RD_EINVAL, "%s: null t_pdflat", fn);
+    if (((uintptr_t)x & 15) != 0) return rd::set_error(RD_EINVAL, "%s: x is not 16-byte aligned", fn);
+    if (((uintptr_t)t_pdflat & 15) != 0) return rd::set_error(RD_EINVAL, "%s: t_pdflat is not 16-byte aligned", fn);
+    if (steps < 1) return rd::set_error(RD_EINVAL, "%s: steps %d < 1", fn, steps);
+    if (act_with != RDM_ACT_TEACHER && act_with != RDM_ACT_STUDENT)
+        return rd::set_error(RD_EINVAL, "%s: unknown act_with %d", fn, act_with);
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "%s: no envs attached (rdm_envs_attach)", fn);
+    if (t->envs_n > ((int64_t)1 << 31) / steps)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs_n);
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdm_set_teacher)", fn);
+    return RD_OK;
+}
+
+// K env steps of every env: a block of envs per workgroup for the whole launch, sized as rdm_evaluate's
+int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward) {
+    SmEnvsArgs a = envs_args(t);
+    a.x = x;
+    a.t_pdflat = t_pdflat;
+    a.s_pdflat = s_pdflat;
+    a.reward = reward;
+    a.steps = steps;
+    const int cap = t->envs_grid > 0 ? t->envs_grid : t->grid;
+    const bool small = eval_small_rows(a.n, cap);
+    const int rows = small ? 16 : 64;
+    const int64_t nblk = (a.n + rows - 1) / rows;
+    const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(small ? ELay<16>::THREADS : ELay<64>::THREADS);
+    const bool stu = act_with == RDM_ACT_STUDENT;
+    if (small && stu) hipLaunchKernelGGL((student_mlp_envs_kernel<16, true>), grid, block, 0, t->stream, a);
+    else if (small) hipLaunchKernelGGL((student_mlp_envs_kernel<16, false>), grid, block, 0, t->stream, a);
+    else if (stu) hipLaunchKernelGGL((student_mlp_envs_kernel<64, true>), grid, block, 0, t->stream, a);
+    else hipLaunchKernelGGL((student_mlp_envs_kernel<64, false>), grid, block, 0, t->stream, a);
+    RD_HIP(hipGetLastError(), "student_mlp_envs_kernel launch");
+    return RD_OK;
+}
+
+// act, then the training launch on the K n rows just written, as rdm_rollout / rdm_step run it
+int envs_train(const char* fn, rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat,
+               float* reward, int adam) {
+    if (int rc = envs_check(fn, t, act_with, steps, x, t_pdflat)) return rc;
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, fn);
+    if (int rc = launch_envs(t, act_with, steps, x, t_pdflat, s_pdflat, reward)) return rc;
+    const int64_t rows = (int64_t)steps * t->envs_n;
+    if (int rc = launch_train(t, x, t_pdflat, rows, rows)) return rc;
+    return launch_adam(t, 1, adam);
+}
+
 }  // namespace
 
 extern "C" {
@@ -687,7 +767,8 @@ int rdm_destroy(rdm_trainer* t) {
     if (!t) return RD_OK;
     rd::DeviceGuard dg(t->device);
     for (void* p : {(void*)t->params, (void*)t->img, (void*)t->m, (void*)t->v, (void*)t->own_grad, (void*)t->ws,
-                    (void*)t->hist, (void*)t->ctl, (void*)t->tnet})
+                    (void*)t->hist, (void*)t->ctl, (void*)t->tnet, (void*)t->env_state, (void*)t->env_aux,
+                    (void*)t->env_clock})
         if (p) (void)hipFree(p);
     delete t;
     return RD_OK;
@@ -871,6 +952,84 @@ int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, flo
     else
         hipLaunchKernelGGL(student_mlp_evaluate_kernel<64>, dim3(grid), dim3(ELay<64>::THREADS), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
+    return RD_OK;
+}
+
+int rdm_envs_reset(rdm_trainer* t) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_reset: null trainer");
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdm_envs_reset: no envs attached (rdm_envs_attach)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_envs_reset");
+    hipLaunchKernelGGL(student_mlp_envs_reset_kernel, dim3((unsigned)((t->envs_n + 255) / 256)), dim3(256), 0, t->stream,
+                       envs_args(t));
+    RD_HIP(hipGetLastError(), "student_mlp_envs_reset_kernel launch");
+    return RD_OK;
+}
+
+int rdm_envs_attach(rdm_trainer* t, const rdm_envs_config* cfg) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_attach: null trainer");
+    if (!cfg) return rd::set_error(RD_EINVAL, "rdm_envs_attach: null config");
+    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
+        return rd::set_error(RD_EINVAL, "rdm_envs_attach: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
+    if (cfg->env_base < 0) return rd::set_error(RD_EINVAL, "rdm_envs_attach: negative env_base");
+    if (cfg->grid < 0) return rd::set_error(RD_EINVAL, "rdm_envs_attach: negative grid");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_envs_attach");
+    if (t->env_state) {   // replace: launches that still read the old envs finish first
+        RD_HIP(hipStreamSynchronize(t->stream), "rdm_envs_attach");
+        for (void* p : {(void*)t->env_state, (void*)t->env_aux, (void*)t->env_clock}) (void)hipFree(p);
+        t->env_state = t->env_aux = nullptr;
+        t->env_clock = nullptr;
+    }
+    const size_t n = (size_t)cfg->n_envs;
+    hipError_t e = hipMalloc((void**)&t->env_state, sizeof(float) * rd::kStateDim * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_aux, sizeof(float) * ENV_AUX * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_clock, sizeof(int32_t) * 2 * n);
+    if (e != hipSuccess) {
+        for (void* p : {(void*)t->env_state, (void*)t->env_aux, (void*)t->env_clock})
+            if (p) (void)hipFree(p);
+        t->env_state = t->env_aux = nullptr;
+        t->env_clock = nullptr;
+        return rd::hip_fail(e, "rdm_envs_attach: allocation");
+    }
+    t->envs_n = cfg->n_envs;
+    t->envs_base = cfg->env_base;
+    t->envs_seed = cfg->seed;
+    t->envs_grid = cfg->grid;
+    return rdm_envs_reset(t);
+}
+
+int rdm_envs_act(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward) {
+    if (int rc = envs_check("rdm_envs_act", t, act_with, steps, x, t_pdflat)) return rc;
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_envs_act");
+    return launch_envs(t, act_with, steps, x, t_pdflat, s_pdflat, reward);
+}
+
+int rdm_rollout_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat,
+                     float* reward) {
+    return envs_train("rdm_rollout_envs", t, act_with, steps, x, t_pdflat, s_pdflat, reward, 0);
+}
+
+int rdm_step_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward) {
+    return envs_train("rdm_step_envs", t, act_with, steps, x, t_pdflat, s_pdflat, reward, 1);
+}
+
+int rdm_envs_get_state(rdm_trainer* t, float* state, int32_t* step, int32_t* episode) {
+    if (!t || !state) return rd::set_error(RD_EINVAL, "rdm_envs_get_state: null trainer or state");
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdm_envs_get_state: no envs attached (rdm_envs_attach)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdm_envs_get_state");
+    RD_HIP(hipMemcpyAsync(state, t->env_state, sizeof(float) * rd::kStateDim * t->envs_n, hipMemcpyDeviceToDevice,
+                          t->stream), "rdm_envs_get_state: copy");
+    int32_t c[2] = {0, 0};
+    RD_HIP(hipMemcpyAsync(&c[0], t->env_clock, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
+           "rdm_envs_get_state: clock");
+    RD_HIP(hipMemcpyAsync(&c[1], t->env_clock + t->envs_n, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
+           "rdm_envs_get_state: clock");
+    RD_HIP(hipStreamSynchronize(t->stream), "rdm_envs_get_state");
+    if (step) *step = c[0];
+    if (episode) *episode = c[1];
     return RD_OK;
 }
 

@@ -17,6 +17,9 @@ fused DistillTrainer path); ``student="mlp"`` is the reference's own ``student_m
 (student_nn.py:51-57) on rows ob | prev_pdflat | prev_rew (StudentMlpTrainer), trained on the
 recorded teacher pdflat with input dropout ``keep_prob`` (reference KEEP_PROB = 0.5).
 
+``train_envs`` is the same distillation of the reference student over many persistent lockstep envs
+(StudentMlpTrainer.step_envs: no dataset, every optimiser step on the rows its envs just produced).
+
 Fixes of the reference as committed: the committed
 graph's (10,20,.) vs (1,20,.) placeholder mismatch is not reproduced -- every row of a [T, B]
 window is a training row; prev_pdflat / prev_rew are the dataset's recorded fields, not the
@@ -107,6 +110,45 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
             if dataset.num_episodes() >= episodes or done:
                 break
     return (sm or tr), dataset, losses
+
+
+# -- the reference student distilled on-policy over many envs ----------------------------------
+def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-4,
+               accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
+               eval_every: int = 0, eval_envs: int = 4096):
+    """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
+    ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
+    ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
+    training launch and Adam; nothing waits on the GPU between steps).  The first ``warmup_steps``
+    optimiser steps are stepped with the teacher's mean (the driver's phase 1), the rest with the
+    student's (phase 2, DAgger).  The default accum_steps = 50 puts all 50 episode phases of the
+    lockstep envs into every batch -- the role ``stagger`` plays in the fused rollout's config.
+    ``teacher``: an MlpPolicyParams (default: the synthetic teacher DistillTrainer defaults to).
+    Returns (trainer, history), history rows (optimiser step, loss, action-MSE, mean step reward) with
+    the loss of the trainer's metrics ring (the sum over the batch's rows for "kl"), the action-MSE
+    the mean over rows and both action dims against the teacher, the reward the mean over the
+    batch's env steps.  With ``eval_every`` > 0 returns (trainer, history, evals): evals rows
+    (optimiser step, mean return of StudentMlpTrainer.evaluate over ``eval_envs`` fresh envs, one
+    episode) after every eval_every-th step -- the reference's average reward per keep_prob."""
+    from .policy import synthetic_teacher
+    n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
+    if steps < 1 or not 0 <= int(warmup_steps) <= steps:
+        raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
+    sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, metrics_len=steps),
+                           device=device)
+    sm.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
+    sm.attach_envs(n, seed=seed, accum_steps=K)
+    rew = torch.zeros(steps, device=sm.device)
+    evals = []
+    for k in range(steps):
+        r = sm.step_envs("teacher" if k < int(warmup_steps) else "student")
+        rew[k] = r.reward.mean()
+        if eval_every and (k + 1) % int(eval_every) == 0:
+            evals.append((k + 1, float(sm.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
+    m = sm.metrics(steps)
+    rew = rew.cpu().tolist()
+    history = [(k + 1, float(m[k, 0]), float(m[k, 1] / (2 * m[k, 2])), rew[k]) for k in range(steps)]
+    return (sm, history, evals) if eval_every else (sm, history)
 
 
 # -- phase 2 on recorded teacher data (no env) ------------------------------------------------

@@ -7,7 +7,8 @@ HIP kernels in csrc/student_mlp.hip.  ``rows()`` is the input concat of mlp_trai
 (dropout(ob) | prev_pdflat | prev_rew; the dropout itself runs inside the kernel).
 
 Multi-GPU: rows sharded contiguously (dist.shard); one all_reduce(SUM) of the flat
-24,380-float gradient per optimiser step.
+24,380-float gradient per optimiser step.  The persistent envs (attach_envs / act_envs /
+rollout_envs / step_envs: batched on-policy distillation, rdm_step_envs) are single-GPU.
 """
 from __future__ import annotations
 
@@ -42,7 +43,20 @@ class RdmEvalConfig(ctypes.Structure):
                 ("grid", I32), ("draws", P)]
 
 
+class RdmEnvsConfig(ctypes.Structure):
+    _fields_ = [("n_envs", I64), ("env_base", I64), ("seed", U64), ("grid", I32)]
+
+
+ACT_WITH = {"teacher": 0, "student": 1}   # RDM_ACT_*
+_ENVS_CALL = (INT, [P, INT, INT, P, P, P, P])
+
 nat.register({
+    "rdm_envs_attach": (INT, [P, ctypes.POINTER(RdmEnvsConfig)]),
+    "rdm_envs_reset": (INT, [P]),
+    "rdm_envs_act": _ENVS_CALL,
+    "rdm_rollout_envs": _ENVS_CALL,
+    "rdm_step_envs": _ENVS_CALL,
+    "rdm_envs_get_state": (INT, [P, P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "rdm_set_teacher": (INT, [P, P, P, P]),
     "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
@@ -81,6 +95,17 @@ def rows(ob, prev_pdflat, prev_rew) -> torch.Tensor:
 
 
 @dataclass
+class EnvsResult:
+    """The buffers one act_envs / rollout_envs / step_envs call filled, step-major: entry [k, i] is
+    env i's k-th step of the call.  They are the trainer's own (attach_envs), rewritten by the next
+    call: clone to keep."""
+    x: torch.Tensor          # [K, n, 16] the undropped rows ob | prev t_pdflat | prev reward
+    t_pdflat: torch.Tensor   # [K, n, 4] the teacher's mean | logstd
+    s_pdflat: torch.Tensor   # [K, n, 4] the student's (0 when the teacher stepped)
+    reward: torch.Tensor     # [K, n]
+
+
+@dataclass
 class StudentMlpConfig:
     loss: str = "kl"            # mlp_train.py:71 (kl_loss); "mse" = action-MSE
     lr: float = 1e-4            # mlp_train.py:75-78
@@ -112,7 +137,8 @@ class StudentMlpTrainer:
             nat.check(self._lib.rdm_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
                                            nat.stream_handle(self.device)), "rdm_create")
         self._h = h
-        self.teacher = None   # evaluate()'s teacher (set_teacher)
+        self.teacher = None   # the teacher of evaluate() and of the envs (set_teacher)
+        self.n_envs, self.accum_steps, self._envs = 0, 0, None   # attach_envs
         self._grad = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdm_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdm_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed) if params is None else params)
@@ -217,6 +243,85 @@ class StudentMlpTrainer:
                                          nat.ptr(res.records) if records else None), "rdm_evaluate")
         self._keep_eval = table   # the launch reads it asynchronously
         return res
+
+    # -- persistent envs: batched on-policy distillation --------------------------------------
+    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 1):
+        """Give the trainer ``n_envs`` persistent lockstep envs (rdm_envs_attach; Philox resets keyed
+        (seed, env_base + i, episode)) at episode 0, and allocate once the buffers every
+        act_envs / rollout_envs / step_envs call fills: ``accum_steps`` = K env steps per call, so K n
+        rows per optimiser step.  K = 50 puts all 50 episode phases of the lockstep envs into every
+        batch.  Attaching again replaces the envs.  Single GPU only."""
+        n, K = int(n_envs), int(accum_steps)
+        if n < 1 or K < 1:
+            raise ValueError("n_envs >= 1 and accum_steps >= 1")
+        if self.world != 1:
+            raise RuntimeError("the persistent envs are single-GPU (no rank-sharded variant)")
+        c = RdmEnvsConfig(n_envs=n, env_base=int(env_base), seed=int(seed) % 2 ** 64, grid=int(grid))
+        self._envs = None   # the handle's old envs go first
+        self._sync_stream()
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.rdm_envs_attach(self._h, ctypes.byref(c)), "rdm_envs_attach")
+        kw = dict(dtype=torch.float32, device=self.device)
+        self._envs = EnvsResult(torch.zeros(K, n, IN_DIM, **kw), torch.zeros(K, n, PDFLAT_SHAPE, **kw),
+                                torch.zeros(K, n, PDFLAT_SHAPE, **kw), torch.zeros(K, n, **kw))
+        self.n_envs, self.accum_steps = n, K
+
+    def reset_envs(self):
+        """Every env back to its episode 0; clocks, carried reward and previous fields to 0."""
+        self._need_envs()
+        self._sync_stream()
+        nat.check(self._lib.rdm_envs_reset(self._h), "rdm_envs_reset")
+
+    def _need_envs(self):
+        if self._envs is None:
+            raise RuntimeError("no envs attached: call attach_envs(n_envs) first")
+
+    def _envs_call(self, name: str, act_with: str, steps) -> EnvsResult:
+        self._need_envs()
+        K = self.accum_steps if steps is None else int(steps)
+        if not 1 <= K <= self.accum_steps:
+            raise ValueError(f"steps must be 1 .. accum_steps = {self.accum_steps}, got {K}")
+        if act_with not in ACT_WITH:
+            raise ValueError(f"act_with must be 'teacher' or 'student', got {act_with!r}")
+        if self.teacher is None:
+            raise RuntimeError(f"{name} needs a teacher: call set_teacher(MlpPolicyParams) first")
+        b = self._envs
+        r = b if K == self.accum_steps else EnvsResult(b.x[:K], b.t_pdflat[:K], b.s_pdflat[:K], b.reward[:K])
+        self._sync_stream()
+        nat.check(getattr(self._lib, name)(self._h, ACT_WITH[act_with], K, nat.ptr(r.x), nat.ptr(r.t_pdflat),
+                                           nat.ptr(r.s_pdflat), nat.ptr(r.reward)), name)
+        return r
+
+    def act_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """K = ``steps`` (default, and at most, ``accum_steps``) env steps of every env in ONE launch
+        (rdm_envs_act), no training and no side effect on the parameters, Adam state, gradient or
+        metrics; the result's tensors are the first K steps of the trainer's buffers.  Per step the teacher labels the
+        observation, the row ob | the teacher's previous pdflat | the previous record's reward field is
+        assembled (zeros at an episode's step 0), and the env is stepped with the student's mean on
+        that row (``"student"``) or with the teacher's (``"teacher"``: the student is not evaluated,
+        s_pdflat is 0).  Envs reset themselves after their step 49.  Bitwise the stepwise loop
+        {DistillTrainer.forward (teacher), rows(), forward(), BatchedReacher.step(mean)}.  Asynchronous
+        on the current stream, capturable; the device keeps the clock, so a replay takes the NEXT steps."""
+        return self._envs_call("rdm_envs_act", act_with, steps)
+
+    def rollout_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """act_envs, then the training launch on the K n rows it wrote: their gradient in grad()."""
+        return self._envs_call("rdm_rollout_envs", act_with, steps)
+
+    def step_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """act_envs, then one optimiser step on the K n rows it wrote: the parameters, gradient,
+        metrics and counter of step(x, t_pdflat) on them (input dropout ``keep_prob`` included)."""
+        return self._envs_call("rdm_step_envs", act_with, steps)
+
+    def env_state(self):
+        """(state [8, n] as BatchedReacher.get_state, env 0's step of the episode, its episode)."""
+        self._need_envs()
+        st = torch.empty(8, self.n_envs, dtype=torch.float32, device=self.device)
+        s, e = ctypes.c_int32(), ctypes.c_int32()
+        self._sync_stream()
+        nat.check(self._lib.rdm_envs_get_state(self._h, nat.ptr(st), ctypes.byref(s), ctypes.byref(e)),
+                  "rdm_envs_get_state")
+        return st, s.value, e.value
 
     def rollout(self, x, t_pdflat, n_global: int | None = None) -> torch.Tensor:
         """Gradient of this rank's rows into grad(); returns the gradient tensor."""
