@@ -165,6 +165,80 @@ typedef struct {
 int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
                  float* records, float* state_out);
 
+/* Batched on-policy distillation of the LSTM student: the handle keeps n_envs persistent envs in
+ * lockstep, and one call takes them through K env steps under the teacher's or the student's mean
+ * action, labels every step with the teacher (rdl_set_teacher), emits the training windows that lie
+ * wholly inside an episode and trains on them: the driver's loop (lstm_train.py:120-204) over many
+ * envs, the counterpart of rdm_envs_* (reacher_student_mlp.h).
+ * Per env the device keeps (rdl_envs_attach allocates, rdl_destroy frees): the physics state, the
+ * reward its last step returned, the clock (step 0..49 of the episode, episode), the query state
+ * (c, h), the teacher's last pdflat, and the raw fields ob[11] | prev[4] of the open episode's last
+ * T records (T = rdl_config.steps).  One env step is exactly one step of rdl_evaluate:
+ *   ob_s = observe(state);  T_s = the teacher's pdflat on ob_s
+ *   window: the last T records of this episode (zero rows before its step 0), prev of record j =
+ *           T_{j-1}, 0 at j = 0
+ *   RDL_ACT_STUDENT: S_s = head T-1 of the forward on that window from the env's carried (c, h),
+ *           which it replaces; r_s = env.step(S_s[0..1])
+ *   RDL_ACT_TEACHER: r_s = env.step(T_s[0..1]); the student is not evaluated, (c, h) stays as it
+ *           was, s_pdflat and stepped_with are written as 0 (the drivers' warm-up)
+ * After its step 49 an env resets, inside that step as rd_step does, from Philox(seed, env_base + i,
+ * episode + 1); (c, h) and the carried reward survive the reset.  The x rows of the carried records
+ * are re-formed from the raw fields with the parameters each call finds, so an optimiser step or
+ * rdl_set_params between calls acts on the next query as it does in the stepwise loop.  The clock is
+ * on the device: no host-side count enters a launch, so a captured call replays the NEXT K steps.
+ * Outputs (device, caller-owned, step-major: row k n_envs + i is env i's k-th step of the call):
+ *   records [K][n_envs][21]  ob[11] | reward | t_pdflat[4] | s_pdflat[4] | stepped_with (the dataset's
+ *           record): reward = the one the env's previous step returned (0 after attach / reset,
+ *           carried over episode resets), stepped_with = 1 (student) or 0 (teacher)
+ *   reward  [K][n_envs]      r_s (may be NULL)
+ * Training windows: the query windows of the steps whose episode step s >= T-1, i.e. records
+ * s-T+1 .. s of one episode (the windows training_batches can draw, start = s-T+1 in [0, 50-T]),
+ * ordered by k among the qualifying steps, then by env, in the trainer's layout with B windows:
+ *   ob_w [T][B][11], prev_w [T][B][4] (prev of the record), t_w [T][B][4] (its own t_pdflat).
+ * The first windows of a call reach into records of earlier calls (the carried history).
+ * Any 50 consecutive lockstep steps hold exactly 51-T qualifying steps, so rdl_rollout_envs and
+ * rdl_step_envs, which require steps % 50 == 0 (and T <= 50), write B = n_envs (steps/50) (51-T)
+ * windows, then run rdl_rollout(ob_w, prev_w, t_w, NULL, B, B) [+ rdl_apply]: zero initial state,
+ * dropout keep_prob keyed (row_base + window, optimiser step); they leave the parameters, gradient,
+ * metrics, counter and rdl_final_state of rdl_step on those windows.  rdl_envs_act takes any steps
+ * >= 1 and writes windows only if the three window buffers are given, with stride and capacity
+ * B = `windows`: as many as the clock yields (windows past B are dropped; fewer leave the rest of
+ * the buffers untouched), n_envs (steps/50) (51-T) when steps is a multiple of 50.
+ * rdl_envs_act has no side effect on parameters, Adam state, gradient, metrics or counter.
+ * Asynchronous on the handle's stream; no allocation outside rdl_envs_attach: capturable.
+ * SINGLE GPU ONLY: there is no rank-sharded variant of these calls.
+ * RD_EINVAL, naming the function and the field: NULL trainer, config or records; n_envs < 1 (or >
+ * 2^31); steps < 1; unknown act_with; negative env_base or grid; window buffers given in part (or
+ * missing from a training call) (all before any device call and before the handle is read); then,
+ * from the handle: no envs attached; no teacher set; rdl_config.steps > RDL_EVAL_MAX_STEPS; steps x
+ * n_envs > 2^31; for the training calls steps % 50 != 0, rdl_config.steps > 50, B > max_windows. */
+#define RDL_ACT_TEACHER 0
+#define RDL_ACT_STUDENT 1
+typedef struct {
+    int64_t n_envs;          /* persistent envs of the handle                               */
+    int64_t env_base;        /* global id of env 0 (Philox key)                             */
+    uint64_t seed;           /* Philox reset seed                                           */
+    int32_t grid;            /* workgroups (16 envs each per pass); 0 = one per CU          */
+} rdl_envs_config;
+
+/* allocate (or replace) the handle's envs, then reset them */
+int rdl_envs_attach(rdl_trainer* t, const rdl_envs_config* cfg);
+/* episode 0 of every env; clock, carried reward, (c, h) and history to 0 */
+int rdl_envs_reset(rdl_trainer* t);
+/* K env steps, no training; ob_w, prev_w, t_w all NULL (no windows) or all given with B = windows */
+int rdl_envs_act(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                 float* t_w, int64_t windows);
+/* act, then rdl_rollout on the B windows written: gradient in rdl_grad_buffer() */
+int rdl_rollout_envs(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w,
+                     float* prev_w, float* t_w);
+/* rdl_rollout_envs + rdl_apply: one optimiser step */
+int rdl_step_envs(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                  float* t_w);
+/* state [8][n_envs] SoA as rd_get_state (device); env 0's clock; host-synchronising */
+int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode);
+/* the envs' query state [2][n_envs][200] = (c, h) (device), asynchronous */
+int rdl_envs_get_query_state(rdl_trainer* t, float* state_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1468,6 +1468,8 @@ constexpr int64_t SPLIT_FLOATS = 16 << 20;  // split-K partials (64 MB)
 
 // the whole-episode evaluation (rdl_evaluate): tch::, lstm_eval_pack_kernel, student_lstm_evaluate_kernel
 #include "student_lstm_eval.h"
+// the persistent envs (rdl_envs_*, rdl_rollout_envs, rdl_step_envs): LsEnvsArgs, student_lstm_envs_kernel
+#include "student_lstm_envs.h"
 
 }  // namespace
 
@@ -1498,6 +1500,14 @@ struct rdl_trainer {
     float* tnet = nullptr;     // rdl_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
     float* eimg = nullptr;     // rdl_evaluate's packed image of Wl [EV_IMG], rebuilt by every call
     bool has_teacher = false;
+    // the persistent envs (rdl_envs_attach)
+    float *env_state = nullptr, *env_aux = nullptr;   // [8][n] SoA; [ENV_AUX][n]
+    int32_t* env_clock = nullptr;                     // [2][n]: step of the episode, episode
+    float* env_q = nullptr;                           // [2][n][U] = (c, h) of the envs' last query
+    float* env_hist = nullptr;                        // [n][T][EH_REC]: the raw fields of the ring's records
+    int64_t envs_n = 0, envs_base = 0;
+    uint64_t envs_seed = 0;
+    int envs_grid = 0;
 };
 
 namespace {
@@ -1782,6 +1792,105 @@ int launch_adam(rdl_trainer* t) {
 
 bool bad_windows(const rdl_trainer* t, int64_t B) { return B <= 0 || B > t->Bmax; }
 
+// ---------------------------------------------------------------- persistent envs
+void free_envs(rdl_trainer* t) {
+    for (void* p : {(void*)t->env_state, (void*)t->env_aux, (void*)t->env_clock, (void*)t->env_q, (void*)t->env_hist})
+        if (p) (void)hipFree(p);
+    t->env_state = t->env_aux = t->env_q = t->env_hist = nullptr;
+    t->env_clock = nullptr;
+}
+
+LsEnvsArgs envs_args(const rdl_trainer* t) {
+    LsEnvsArgs a{};
+    a.n = t->envs_n;
+    a.env_base = t->envs_base;
+    a.seed = t->envs_seed;
+    a.tnet = t->tnet;
+    a.P = t->params;
+    a.img = t->eimg;
+    a.state = t->env_state;
+    a.aux = t->env_aux;
+    a.clock = t->env_clock;
+    a.q = t->env_q;
+    a.hist = t->env_hist;
+    a.T = t->T;
+    return a;
+}
+
+// The argument checks of rdl_envs_act / rdl_rollout_envs / rdl_step_envs, `fn` naming the caller:
+// everything that needs no handle first, then what the handle says.  train: the two training calls
+// (window buffers required, steps a multiple of the episode); *B: the windows the call writes.
+int envs_check(const char* fn, const rdl_trainer* t, int act_with, int steps, const float* records, const float* ob_w,
+               const float* prev_w, const float* t_w, bool train, int64_t* B) {
+    if (!t) return rd::set_error(RD_EINVAL, "%s: null trainer", fn);
+    if (!records) return rd::set_error(RD_EINVAL, "%s: null records", fn);
+    if (steps < 1) return rd::set_error(RD_EINVAL, "%s: steps %d < 1", fn, steps);
+    if (act_with != RDL_ACT_TEACHER && act_with != RDL_ACT_STUDENT)
+        return rd::set_error(RD_EINVAL, "%s: unknown act_with %d", fn, act_with);
+    if (train ? !ob_w || !prev_w || !t_w : (ob_w || prev_w || t_w) && (!ob_w || !prev_w || !t_w))
+        return rd::set_error(RD_EINVAL, "%s: null ob_w, prev_w or t_w (the window buffers go together)", fn);
+    if (!train && ob_w && *B < 1) return rd::set_error(RD_EINVAL, "%s: windows %lld < 1", fn, (long long)*B);
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "%s: no envs attached (rdl_envs_attach)", fn);
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdl_set_teacher)", fn);
+    if (t->T > EV_MAX_T)
+        return rd::set_error(RD_EINVAL, "%s: rdl_config.steps = %d unrolled steps, the kernel keeps at most %d records "
+                                        "of history", fn, t->T, EV_MAX_T);
+    if (t->envs_n > ((int64_t)1 << 31) / steps)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs_n);
+    if (train) {
+        if (steps % rd::kEpisodeSteps)
+            return rd::set_error(RD_EINVAL, "%s: steps %d is not a multiple of the episode's %d", fn, steps,
+                                 rd::kEpisodeSteps);
+        if (t->T > rd::kEpisodeSteps)
+            return rd::set_error(RD_EINVAL, "%s: rdl_config.steps = %d exceeds the episode's %d steps", fn, t->T,
+                                 rd::kEpisodeSteps);
+        *B = t->envs_n * (steps / rd::kEpisodeSteps) * (rd::kEpisodeSteps + 1 - t->T);
+        if (*B > t->Bmax)
+            return rd::set_error(RD_EINVAL, "%s: %lld windows > rdl_config.max_windows = %lld", fn, (long long)*B,
+                                 (long long)t->Bmax);
+    }
+    return RD_OK;
+}
+
+// K env steps of every env: a block of 16 envs per workgroup for the whole launch, one workgroup
+// per CU (its LDS), as rdl_evaluate
+int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                float* t_w, int64_t B) {
+    const bool stu = act_with == RDL_ACT_STUDENT;
+    if (stu) {
+        hipLaunchKernelGGL(lstm_eval_pack_kernel, dim3((EV_IMG + 255) / 256), dim3(256), 0, t->stream,
+                           (const float*)t->params, t->eimg);
+        RD_HIP(hipGetLastError(), "lstm_eval_pack_kernel launch");
+    }
+    LsEnvsArgs a = envs_args(t);
+    a.records = records;
+    a.reward = reward;
+    a.ob_w = ob_w;
+    a.prev_w = prev_w;
+    a.t_w = t_w;
+    a.windows = ob_w ? B : 0;
+    a.steps = steps;
+    const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = t->envs_grid > 0 ? t->envs_grid : t->cus;
+    const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
+    if (stu) hipLaunchKernelGGL(student_lstm_envs_kernel<true>, grid, block, 0, t->stream, a);
+    else hipLaunchKernelGGL(student_lstm_envs_kernel<false>, grid, block, 0, t->stream, a);
+    RD_HIP(hipGetLastError(), "student_lstm_envs_kernel launch");
+    return RD_OK;
+}
+
+// act, then the training path on the B windows just written, as rdl_rollout / rdl_step run it
+int envs_train(const char* fn, rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w,
+               float* prev_w, float* t_w, int adam) {
+    int64_t B = 0;
+    if (int rc = envs_check(fn, t, act_with, steps, records, ob_w, prev_w, t_w, true, &B)) return rc;
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, fn);
+    if (int rc = launch_envs(t, act_with, steps, records, reward, ob_w, prev_w, t_w, B)) return rc;
+    if (int rc = run_forward(t, ob_w, prev_w, nullptr, B, t->Y, true, t_w, B)) return rc;
+    if (int rc = run_backward(t, prev_w, t_w, B, B)) return rc;
+    return adam ? launch_adam(t) : RD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1888,6 +1997,7 @@ int rdl_destroy(rdl_trainer* t) {
                      t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack, t->tnet, t->eimg};
     for (float* p : bufs)
         if (p) (void)hipFree(p);
+    free_envs(t);
     if (t->hx) (void)hipFree(t->hx);
     if (t->ctl) (void)hipFree(t->ctl);
     if (t->bar) (void)hipFree(t->bar);
@@ -2102,6 +2212,97 @@ int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0
     hipLaunchKernelGGL(student_lstm_evaluate_kernel, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0,
                        t->stream, a);
     RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
+    return RD_OK;
+}
+
+int rdl_envs_reset(rdl_trainer* t) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_reset: null trainer");
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_reset: no envs attached (rdl_envs_attach)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_envs_reset");
+    const size_t n = (size_t)t->envs_n;
+    RD_HIP(hipMemsetAsync(t->env_q, 0, sizeof(float) * 2 * n * U, t->stream), "rdl_envs_reset: query state");
+    RD_HIP(hipMemsetAsync(t->env_hist, 0, sizeof(float) * n * t->T * EH_REC, t->stream), "rdl_envs_reset: history");
+    hipLaunchKernelGGL(student_lstm_envs_reset_kernel, dim3((unsigned)((t->envs_n + 255) / 256)), dim3(256), 0, t->stream,
+                       envs_args(t));
+    RD_HIP(hipGetLastError(), "student_lstm_envs_reset_kernel launch");
+    return RD_OK;
+}
+
+int rdl_envs_attach(rdl_trainer* t, const rdl_envs_config* cfg) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_attach: null trainer");
+    if (!cfg) return rd::set_error(RD_EINVAL, "rdl_envs_attach: null config");
+    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
+        return rd::set_error(RD_EINVAL, "rdl_envs_attach: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
+    if (cfg->env_base < 0) return rd::set_error(RD_EINVAL, "rdl_envs_attach: negative env_base");
+    if (cfg->grid < 0) return rd::set_error(RD_EINVAL, "rdl_envs_attach: negative grid");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_envs_attach");
+    if (t->env_state) {   // replace: launches that still read the old envs finish first
+        RD_HIP(hipStreamSynchronize(t->stream), "rdl_envs_attach");
+        free_envs(t);
+    }
+    const size_t n = (size_t)cfg->n_envs;
+    hipError_t e = hipMalloc((void**)&t->env_state, sizeof(float) * rd::kStateDim * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_aux, sizeof(float) * ENV_AUX * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_clock, sizeof(int32_t) * 2 * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_q, sizeof(float) * 2 * n * U);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->env_hist, sizeof(float) * n * t->T * EH_REC);
+    if (e != hipSuccess) {
+        free_envs(t);
+        return rd::hip_fail(e, "rdl_envs_attach: allocation");
+    }
+    t->envs_n = cfg->n_envs;
+    t->envs_base = cfg->env_base;
+    t->envs_seed = cfg->seed;
+    t->envs_grid = cfg->grid;
+    return rdl_envs_reset(t);
+}
+
+int rdl_envs_act(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                 float* t_w, int64_t windows) {
+    int64_t B = windows;
+    if (int rc = envs_check("rdl_envs_act", t, act_with, steps, records, ob_w, prev_w, t_w, false, &B)) return rc;
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_envs_act");
+    return launch_envs(t, act_with, steps, records, reward, ob_w, prev_w, t_w, B);
+}
+
+int rdl_rollout_envs(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                     float* t_w) {
+    return envs_train("rdl_rollout_envs", t, act_with, steps, records, reward, ob_w, prev_w, t_w, 0);
+}
+
+int rdl_step_envs(rdl_trainer* t, int act_with, int steps, float* records, float* reward, float* ob_w, float* prev_w,
+                  float* t_w) {
+    return envs_train("rdl_step_envs", t, act_with, steps, records, reward, ob_w, prev_w, t_w, 1);
+}
+
+int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode) {
+    if (!t || !state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: null trainer or state");
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: no envs attached (rdl_envs_attach)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_envs_get_state");
+    RD_HIP(hipMemcpyAsync(state, t->env_state, sizeof(float) * rd::kStateDim * t->envs_n, hipMemcpyDeviceToDevice,
+                          t->stream), "rdl_envs_get_state: copy");
+    int32_t c[2] = {0, 0};
+    RD_HIP(hipMemcpyAsync(&c[0], t->env_clock, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
+           "rdl_envs_get_state: clock");
+    RD_HIP(hipMemcpyAsync(&c[1], t->env_clock + t->envs_n, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
+           "rdl_envs_get_state: clock");
+    RD_HIP(hipStreamSynchronize(t->stream), "rdl_envs_get_state");
+    if (step) *step = c[0];
+    if (episode) *episode = c[1];
+    return RD_OK;
+}
+
+int rdl_envs_get_query_state(rdl_trainer* t, float* state_out) {
+    if (!t || !state_out) return rd::set_error(RD_EINVAL, "rdl_envs_get_query_state: null trainer or state_out");
+    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_get_query_state: no envs attached (rdl_envs_attach)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_envs_get_query_state");
+    RD_HIP(hipMemcpyAsync(state_out, t->env_q, sizeof(float) * 2 * t->envs_n * U, hipMemcpyDeviceToDevice, t->stream),
+           "rdl_envs_get_query_state: copy");
     return RD_OK;
 }
 

@@ -15,6 +15,9 @@ Phases as in the reference:
 Fixes of the reference as committed: the test window's prev_pdflat column is
 the per-step series (``DeviceDataset.test_windows``), not the single element that only
 broadcasts at 0 or >= T-1 records.
+
+``train_envs`` is the batched form: many persistent lockstep envs, one
+``StudentLstmTrainer.step_envs`` call per optimiser step (single GPU).
 """
 from __future__ import annotations
 
@@ -106,6 +109,52 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
             if dataset.num_episodes() >= episodes:
                 break
     return st, dataset, losses
+
+
+# -- the LSTM student distilled on-policy over many envs ---------------------------------------
+def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-3,
+               accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
+               eval_every: int = 0, eval_envs: int = 4096):
+    """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
+    ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
+    StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
+    launch, then the training pass and Adam on the query windows that lie inside an episode, from a
+    zero initial state as lstm_train.py:159; nothing waits on the GPU between steps.  The first
+    ``warmup_steps`` optimiser steps are stepped with the teacher's mean (the driver's phase 1: the
+    student is not evaluated), the rest with the student's (phase 2, DAgger).
+    Cost: every 50 env steps of an env hold 51 - T training windows, so a step trains on
+    B = n_envs (accum_steps / 50) (51 - T) windows -- 41 x n_envs at T = 10 and accum_steps = 50 -- and
+    the trainer is created with ``max_windows`` = B.  Its activations are about 2,900 floats per
+    window position, 116 KB per window at T = 10: 4.8 MB per env, 1.2 GB at 256 envs, 19 GB at 4,096;
+    T x B is at most 2^22 (n_envs <= 10,229 at the defaults).  A few hundred envs is the modest choice.
+    ``teacher``: an MlpPolicyParams (default: the synthetic teacher DistillTrainer defaults to).
+    Returns (trainer, history), history rows (optimiser step, loss, action-MSE, mean step reward) with
+    the loss of the trainer's metrics ring (the sum over the batch's T x B rows for "kl"), the
+    action-MSE the mean over rows and both action dims against the teacher, the reward the mean over
+    the call's env steps.  With ``eval_every`` > 0 returns (trainer, history, evals): evals rows
+    (optimiser step, mean return of StudentLstmTrainer.evaluate over ``eval_envs`` fresh envs, one
+    episode) after every eval_every-th step.  Single GPU."""
+    from .policy import synthetic_teacher
+    n, steps, K, T = int(n_envs), int(opt_steps), int(accum_steps), STEPS_UNROLLED
+    if steps < 1 or not 0 <= int(warmup_steps) <= steps:
+        raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
+    if n < 1 or K < 50 or K % 50:
+        raise ValueError("n_envs >= 1 and accum_steps a positive multiple of 50")
+    st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, steps=T,
+                                              max_windows=n * (K // 50) * (51 - T), metrics_len=steps), device=device)
+    st.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
+    st.attach_envs(n, seed=seed, accum_steps=K)
+    rew = torch.zeros(steps, device=st.device)
+    evals = []
+    for k in range(steps):
+        r = st.step_envs("teacher" if k < int(warmup_steps) else "student")
+        rew[k] = r.reward.mean()
+        if eval_every and (k + 1) % int(eval_every) == 0:
+            evals.append((k + 1, float(st.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
+    m = st.metrics(steps)
+    rew = rew.cpu().tolist()
+    history = [(k + 1, float(m[k, 0]), float(m[k, 1] / (2 * m[k, 2])), rew[k]) for k in range(steps)]
+    return (st, history, evals) if eval_every else (st, history)
 
 
 def train_bptt(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EPISODES, loss: str = "kl",

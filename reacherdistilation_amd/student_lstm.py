@@ -61,7 +61,21 @@ class RdlEvalConfig(ctypes.Structure):
                 ("grid", I32), ("draws", P)]
 
 
+class RdlEnvsConfig(ctypes.Structure):
+    _fields_ = [("n_envs", I64), ("env_base", I64), ("seed", U64), ("grid", I32)]
+
+
+ACT_WITH = {"teacher": 0, "student": 1}   # RDL_ACT_*
+_ENVS_TRAIN = (INT, [P, INT, INT, P, P, P, P, P])
+
 nat.register({
+    "rdl_envs_attach": (INT, [P, ctypes.POINTER(RdlEnvsConfig)]),
+    "rdl_envs_reset": (INT, [P]),
+    "rdl_envs_act": (INT, [P, INT, INT, P, P, P, P, P, I64]),
+    "rdl_rollout_envs": _ENVS_TRAIN,
+    "rdl_step_envs": _ENVS_TRAIN,
+    "rdl_envs_get_state": (INT, [P, P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+    "rdl_envs_get_query_state": (INT, [P, P]),
     "rdl_set_teacher": (INT, [P, P, P, P]),
     "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
     "rdl_param_count": (I64, [I32]),
@@ -97,6 +111,19 @@ def glorot_init(seed: int = 3, T: int = STEPS_UNROLLED) -> np.ndarray:
         else:
             out.append(np.zeros(s, np.float32))
     return np.concatenate(out)
+
+
+@dataclass
+class EnvsResult:
+    """The buffers one act_envs / rollout_envs / step_envs call filled.  records and reward are
+    step-major: entry [k, i] is env i's k-th step of the call.  The window tensors (None when the call
+    wrote none) hold the query windows that lie wholly inside an episode, ordered by step, then by env.
+    They are the trainer's own (attach_envs), rewritten by the next call: clone to keep."""
+    records: torch.Tensor            # [K, n, 21] ob[11] | reward | t_pdflat[4] | s_pdflat[4] | stepped_with
+    reward: torch.Tensor             # [K, n]
+    ob_w: torch.Tensor | None        # [T, B, 11]
+    prev_w: torch.Tensor | None      # [T, B, 4] the previous record's t_pdflat (0 at an episode's step 0)
+    t_w: torch.Tensor | None         # [T, B, 4] the records' own t_pdflat
 
 
 @dataclass
@@ -139,6 +166,7 @@ class StudentLstmTrainer:
                                            nat.stream_handle(self.device)), "rdl_create")
         self._h = h
         self.teacher = None   # evaluate()'s teacher (set_teacher)
+        self._envs = None     # attach_envs()'s buffers
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -326,6 +354,116 @@ class StudentLstmTrainer:
                                          nat.ptr(res.state) if final_state else None), "rdl_evaluate")
         self._keep_eval = (table, state0)   # the launch reads them asynchronously
         return res
+
+    # -- persistent envs: batched on-policy distillation --------------------------------------
+    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 50):
+        """Give the trainer ``n_envs`` persistent lockstep envs (rdl_envs_attach; Philox resets keyed
+        (seed, env_base + i, episode)) at episode 0 with a zero query state, and allocate once the
+        buffers every act_envs / rollout_envs / step_envs call fills: ``accum_steps`` = K env steps
+        per call at the most.  A call of a multiple of 50 steps holds n (K / 50) (51 - T) training
+        windows (any 50 consecutive lockstep steps hold 51 - T queries whose window lies inside one
+        episode); ``max_windows`` of the config must cover that for the training calls.  Attaching
+        again replaces the envs.  Single GPU only."""
+        n, K = int(n_envs), int(accum_steps)
+        if n < 1 or K < 1:
+            raise ValueError("n_envs >= 1 and accum_steps >= 1")
+        if self.world != 1:
+            raise RuntimeError("the persistent envs are single-GPU (no rank-sharded variant)")
+        c = RdlEnvsConfig(n_envs=n, env_base=int(env_base), seed=int(seed) % 2 ** 64, grid=int(grid))
+        self._envs = None   # the handle's old envs go first
+        self._sync_stream()
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.rdl_envs_attach(self._h, ctypes.byref(c)), "rdl_envs_attach")
+        kw = dict(dtype=torch.float32, device=self.device)
+        T = self.T
+        Bm = n * (K // 50) * (51 - T) if T <= 50 else 0   # windows of the longest multiple-of-50 call
+        self._envs = EnvsResult(torch.zeros(K, n, 21, **kw), torch.zeros(K, n, **kw),
+                                torch.zeros(T * Bm * OBSPACE_SHAPE, **kw) if Bm else None,
+                                torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None,
+                                torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None)
+        self.n_envs, self.accum_steps = n, K
+
+    def reset_envs(self):
+        """Every env back to its episode 0; clock, carried reward, query state and history to 0."""
+        self._need_envs()
+        self._sync_stream()
+        nat.check(self._lib.rdl_envs_reset(self._h), "rdl_envs_reset")
+
+    def _need_envs(self):
+        if self._envs is None:
+            raise RuntimeError("no envs attached: call attach_envs(n_envs) first")
+
+    def _envs_call(self, name: str, act_with: str, steps) -> EnvsResult:
+        self._need_envs()
+        K = self.accum_steps if steps is None else int(steps)
+        if not 1 <= K <= self.accum_steps:
+            raise ValueError(f"steps must be 1 .. accum_steps = {self.accum_steps}, got {K}")
+        if act_with not in ACT_WITH:
+            raise ValueError(f"act_with must be 'teacher' or 'student', got {act_with!r}")
+        if self.teacher is None:
+            raise RuntimeError(f"{name} needs a teacher: call set_teacher(MlpPolicyParams) first")
+        b, T = self._envs, self.T
+        train = name != "rdl_envs_act"
+        B = self.n_envs * (K // 50) * (51 - T) if K % 50 == 0 and T <= 50 else 0   # windows only for whole episodes' worth
+        dims = (OBSPACE_SHAPE, PDFLAT_SHAPE, PDFLAT_SHAPE)
+        if B:
+            w = [x[:T * B * d].view(T, B, d) for x, d in zip((b.ob_w, b.prev_w, b.t_w), dims)]
+        elif train:   # no whole episode's worth of steps: the library names what is wrong, given any buffers
+            w = [torch.zeros(T, 1, d, dtype=torch.float32, device=self.device) for d in dims]
+        else:
+            w = [None, None, None]
+        r = EnvsResult(b.records[:K], b.reward[:K], *(w if B else [None, None, None]))
+        self._sync_stream()
+        args = [self._h, ACT_WITH[act_with], K, nat.ptr(r.records), nat.ptr(r.reward)] + \
+               [nat.ptr(x) if x is not None else None for x in w]
+        if not train:
+            args.append(B)
+        nat.check(getattr(self._lib, name)(*args), name)
+        return r
+
+    def act_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """K = ``steps`` (default, and at most, ``accum_steps``) env steps of every env in ONE launch
+        (rdl_envs_act), no training and no side effect on the parameters, Adam state, gradient, metrics
+        or counter.  Per step the teacher labels the observation; under ``"student"`` the window of the
+        episode's last T records (zero rows before its first) runs from the env's carried (c, h) and
+        the mean of unrolled position T-1 steps the env; under ``"teacher"`` the teacher's mean does,
+        the student is not evaluated, (c, h) stays, s_pdflat and stepped_with are 0.  Envs reset
+        themselves after their step 49; (c, h) carries over.  The x rows of the carried records are
+        re-formed with the parameters the call finds.  Bitwise the stepwise loop
+        {DistillTrainer.forward (teacher), the window, forward(ob_w, prev_w, state)[T-1],
+        BatchedReacher.step(mean)}.  The result's window tensors are filled when ``steps`` is a
+        multiple of 50 (B = n (steps / 50) (51 - T)), else None.  Asynchronous on the current stream,
+        capturable; the device keeps the clock, so a replay takes the NEXT steps."""
+        return self._envs_call("rdl_envs_act", act_with, steps)
+
+    def rollout_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """act_envs (``steps`` a multiple of 50), then the training pass on the windows it wrote, from
+        a zero initial state: their gradient in grad()."""
+        return self._envs_call("rdl_rollout_envs", act_with, steps)
+
+    def step_envs(self, act_with: str = "student", steps: int | None = None) -> EnvsResult:
+        """act_envs (``steps`` a multiple of 50), then one optimiser step on the windows it wrote: the
+        parameters, gradient, metrics, counter and final_state of step(ob_w, prev_w, t_w) on them
+        (input dropout ``keep_prob`` included)."""
+        return self._envs_call("rdl_step_envs", act_with, steps)
+
+    def env_state(self):
+        """(state [8, n] as BatchedReacher.get_state, env 0's step of the episode, its episode)."""
+        self._need_envs()
+        st = torch.empty(8, self.n_envs, dtype=torch.float32, device=self.device)
+        s, e = ctypes.c_int32(), ctypes.c_int32()
+        self._sync_stream()
+        nat.check(self._lib.rdl_envs_get_state(self._h, nat.ptr(st), ctypes.byref(s), ctypes.byref(e)),
+                  "rdl_envs_get_state")
+        return st, s.value, e.value
+
+    def query_state(self) -> torch.Tensor:
+        """[2, n, 200] = (c, h) of the envs after their last student query (zeros after attach / reset)."""
+        self._need_envs()
+        out = torch.empty(2, self.n_envs, NUM_UNITS, dtype=torch.float32, device=self.device)
+        self._sync_stream()
+        nat.check(self._lib.rdl_envs_get_query_state(self._h, nat.ptr(out)), "rdl_envs_get_query_state")
+        return out
 
     def rollout(self, ob, prev_pdflat, t_pdflat, state0=None, windows_global: int | None = None):
         ob, prev, tgt, st, B = self._windows(ob, prev_pdflat, t_pdflat, state0)
