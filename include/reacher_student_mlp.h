@@ -14,6 +14,19 @@
  * or action-MSE: sum over rows of |mu_s - mu_t|^2 / (2 n_global).
  * Optimiser: TF1 Adam (mlp_train.py:73-80), f32 master weights and slots.
  *
+ * Arithmetic (the dtype of rdm_create_dtype).  RDM_DTYPE_F32 (rdm_create): exact f32 products everywhere.
+ * RDM_DTYPE_BF16, mixed precision: master weights, Adam slots, biases, tanh, the loss, db and every
+ * accumulation stay f32.  Layers 0 (16->24) and 4 (32->4), 2.1 % of the MACs, keep the f32 products
+ * (forward, dW, db, layer 4's dgrad), so neither the raw inputs nor the emitted mean and log-std are
+ * cut to 8 bits.  Layers 1, 2, 3 (24->128, 128->128, 128->32) round their matrix operands to bf16,
+ * bf = round-to-nearest-even (v_cvt_pk_bf16_f32), products exact, sums f32:
+ *     forward  z  = b + sum_k bf(x_k) bf(W_kc)
+ *     dgrad    dH = sum_m bf(dZ_m) bf(W_cm),  dZ = dH (1 - H^2) with the f32 activation H
+ *     wgrad    dW = sum_rows bf(H) bf(dZ),    db = sum_rows dZ (unrounded)
+ * The bf16 weights are roundings of the master, re-formed by rdm_set_params and every Adam step.
+ * Every path of the handle runs the same forward: rdm_forward, the training launch, rdm_evaluate
+ * and the envs calls, so the bitwise contracts below hold in either mode.  The teacher stays f32.
+ *
  * Conventions as in reacher.h: device pointers (x 16-byte aligned), asynchronous on the
  * handle's stream, 0 = OK, RD_EINVAL, -(hipError_t).  Multi-GPU: rows sharded by the
  * caller; per step rdm_rollout(), all-reduce(SUM) rdm_grad_buffer(), rdm_apply().
@@ -33,6 +46,8 @@ extern "C" {
 #define RDM_OUT 4
 #define RDM_LOSS_MSE 0
 #define RDM_LOSS_KL 1
+#define RDM_DTYPE_F32 0
+#define RDM_DTYPE_BF16 1
 
 typedef struct {
     int32_t loss;                  /* RDM_LOSS_*                                         */
@@ -52,8 +67,12 @@ typedef struct {
 typedef struct rdm_trainer rdm_trainer;
 
 int rdm_param_count(void);
-/* the 'MLP' scope: student graph, loss and Adam (mlp_train.py:35-80) */
+/* the 'MLP' scope: student graph, loss and Adam (mlp_train.py:35-80), in f32 */
 int rdm_create(rdm_trainer** out, const rdm_config* cfg, int device, void* hip_stream);
+/* rdm_create with the arithmetic of layers 1-3 chosen (RDM_DTYPE_*, "Arithmetic" above); RD_EINVAL for
+ * another value.  rdm_config keeps its layout, so callers of rdm_create need no rebuild, and
+ * rdm_create(cfg) == rdm_create_dtype(cfg, RDM_DTYPE_F32). */
+int rdm_create_dtype(rdm_trainer** out, const rdm_config* cfg, int32_t dtype, int device, void* hip_stream);
 int rdm_destroy(rdm_trainer* t);
 int rdm_set_stream(rdm_trainer* t, void* hip_stream);
 /* variable initialisation / restore (mlp_train.py:82-99): params [RDM_PARAMS] */

@@ -18,7 +18,9 @@
 //    registers across the workgroup's row blocks; bias gradients are per-thread column
 //    sums.  One workspace row per workgroup, summed in a fixed order by the Adam kernel
 //    (deterministic, no atomics);
-//  * exact f32 products (f32-input MFMA); tanh = 1 - 2 / (2^(2 log2(e) z) + 1).
+//  * exact f32 products (f32-input MFMA); tanh = 1 - 2 / (2^(2 log2(e) z) + 1);
+//  * rdm_create_dtype(.., RDM_DTYPE_BF16, ..): the three wide layers run on v_mfma_f32_16x16x32_bf16
+//    instead (student_mlp_bf16.h), in BF = true instances of the same kernels.
 // The closed-loop evaluation over whole episodes (rdm_evaluate) is in student_mlp_eval.h, the
 // persistent envs of the batched on-policy step (rdm_step_envs) in student_mlp_envs.h.
 #include <hip/hip_runtime.h>
@@ -273,12 +275,33 @@ __device__ __forceinline__ void bgrad_layer(const float* D, float& gb, int tid) 
     }
 }
 
+// the bf16 siblings of the three layer templates above, and the bf16 weight image
+#include "student_mlp_bf16.h"
+
+// Layer L in the arithmetic of the instance: BF takes layers 1..3 to their bf16 siblings.
+template <bool BF, int RB, int L, int SI, int SO, bool FENCE = false>
+__device__ __forceinline__ void fwd(const float* X, float* Y, const float* img, int wave, int i, int g) {
+    if constexpr (BF && is_bf_layer(L)) fwd_layer_bf<RB, L, SI, SO>(X, Y, img, wave, i, g);
+    else fwd_layer<RB, L, SI, SO, FENCE>(X, Y, img, wave, i, g);
+}
+template <bool BF, int RB, int L, int SD, int SH, int SO>
+__device__ __forceinline__ void dgrad(const float* D, const float* H, float* out, const float* img, int wave, int i,
+                                      int g) {
+    if constexpr (BF && is_bf_layer(L)) dgrad_layer_bf<RB, L, SD, SH, SO>(D, H, out, img, wave, i, g);
+    else dgrad_layer<RB, L, SD, SH, SO>(D, H, out, img, wave, i, g);
+}
+template <bool BF, int ROWS, int L, int SH, int SD>
+__device__ __forceinline__ void wgrad(const float* H, const float* D, f32x4 (&G)[WG<L>::Q], int wave, int i, int g) {
+    if constexpr (BF && is_bf_layer(L)) wgrad_layer_bf<ROWS, L, SH, SD>(H, D, G, wave, i, g);
+    else wgrad_layer<ROWS, L, SH, SD>(H, D, G, wave, i, g);
+}
+
 struct SmArgs {
     const float* x;        // [n][16]
     const float* tgt;      // [n][4] teacher pdflat (training)
     float* out;            // [n][4] pdflat (forward)
     int64_t n;
-    const float* img;      // weight image [IMG]
+    const float* img;      // weight image [IMG_ALL]: f32, then the bf16 images
     float* ws;             // [gridDim.x][WS_ROW] partials (training)
     uint32_t* ctl;
     int loss;
@@ -288,7 +311,7 @@ struct SmArgs {
     int64_t row_base;
 };
 
-template <bool TRAIN, int ROWS>
+template <bool TRAIN, int ROWS, bool BF>
 __global__ __launch_bounds__(BLOCK) void student_mlp_kernel(SmArgs a) {
     using LY = Lay<ROWS>;
     constexpr int RB = LY::RB;
@@ -332,15 +355,15 @@ __global__ __launch_bounds__(BLOCK) void student_mlp_kernel(SmArgs a) {
             for (int k = 0; k < 4; ++k) X0[r * S_X0 + pk(4 * c + k)] = v[k];
         }
         __syncthreads();
-        fwd_layer<RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
+        fwd<BF, RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
         __syncthreads();
-        fwd_layer<RB, 1, S_X1, S_X2>(X1, X2, a.img, wave, i, g);
+        fwd<BF, RB, 1, S_X1, S_X2>(X1, X2, a.img, wave, i, g);
         __syncthreads();
-        fwd_layer<RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
+        fwd<BF, RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
         __syncthreads();
-        fwd_layer<RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
+        fwd<BF, RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
         __syncthreads();
-        fwd_layer<RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
+        fwd<BF, RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
         __syncthreads();
         if constexpr (!TRAIN) {
             // the next block's first write (X0) is ordered after this block's F0 by the barriers above
@@ -379,27 +402,27 @@ __global__ __launch_bounds__(BLOCK) void student_mlp_kernel(SmArgs a) {
             }
             __syncthreads();
             // layer 4 (32 -> 4): dW4, db4, dZ4 = (dZ5 W4^T) * (1 - H4^2)
-            wgrad_layer<ROWS, 4, S_X4, S_D5>(X4, D5, G4, wave, i, g);
+            wgrad<BF, ROWS, 4, S_X4, S_D5>(X4, D5, G4, wave, i, g);
             bgrad_layer<ROWS, 4, S_D5>(D5, gb4, tid);
-            dgrad_layer<RB, 4, S_D5, S_X4, S_D4>(D5, X4, D4, a.img, wave, i, g);
+            dgrad<BF, RB, 4, S_D5, S_X4, S_D4>(D5, X4, D4, a.img, wave, i, g);
             __syncthreads();
             // layer 3 (128 -> 32): dZ3 = dZ4 W3^T (H3 is linear)
-            wgrad_layer<ROWS, 3, S_X3, S_D4>(X3, D4, G3, wave, i, g);
+            wgrad<BF, ROWS, 3, S_X3, S_D4>(X3, D4, G3, wave, i, g);
             bgrad_layer<ROWS, 3, S_D4>(D4, gb3, tid);
-            dgrad_layer<RB, 3, S_D4, S_X3, S_DA>(D4, X3, DA, a.img, wave, i, g);
+            dgrad<BF, RB, 3, S_D4, S_X3, S_DA>(D4, X3, DA, a.img, wave, i, g);
             __syncthreads();
             // layer 2 (128 -> 128): dZ2 = (dZ3 W2^T) * (1 - H2^2) into X3's buffer (H3 is dead)
-            wgrad_layer<ROWS, 2, S_X2, S_DA>(X2, DA, G2, wave, i, g);
+            wgrad<BF, ROWS, 2, S_X2, S_DA>(X2, DA, G2, wave, i, g);
             bgrad_layer<ROWS, 2, S_DA>(DA, gb2, tid);
-            dgrad_layer<RB, 2, S_DA, S_X2, S_X3>(DA, X2, X3, a.img, wave, i, g);
+            dgrad<BF, RB, 2, S_DA, S_X2, S_X3>(DA, X2, X3, a.img, wave, i, g);
             __syncthreads();
             // layer 1 (24 -> 128): dZ1 = (dZ2 W1^T) * (1 - H1^2) into DA
-            wgrad_layer<ROWS, 1, S_X1, S_X3>(X1, X3, G1, wave, i, g);
+            wgrad<BF, ROWS, 1, S_X1, S_X3>(X1, X3, G1, wave, i, g);
             bgrad_layer<ROWS, 1, S_X3>(X3, gb1, tid);
-            dgrad_layer<RB, 1, S_X3, S_X1, S_DA>(X3, X1, DA, a.img, wave, i, g);
+            dgrad<BF, RB, 1, S_X3, S_X1, S_DA>(X3, X1, DA, a.img, wave, i, g);
             __syncthreads();
             // layer 0 (16 -> 24)
-            wgrad_layer<ROWS, 0, S_X0, S_DA>(X0, DA, G0, wave, i, g);
+            wgrad<BF, ROWS, 0, S_X0, S_DA>(X0, DA, G0, wave, i, g);
             bgrad_layer<ROWS, 0, S_DA>(DA, gb0, tid);
             __syncthreads();
         }
@@ -471,9 +494,23 @@ __device__ __forceinline__ void store_param(float* img, const PIdx& ix, float w)
     if (ix.b >= 0) img[ix.b] = w;
 }
 
+// BF: the bf16 images of layers 1..3 are re-formed with the f32 image (roundings of the same master)
+template <bool BF>
+__device__ __forceinline__ void store_param(float* img, int p, const PIdx& ix, float w) {
+    store_param(img, ix, w);
+    if constexpr (BF) {
+        if (ix.b >= 0 && p >= PW[1] && p < PW[4]) {
+            const int L = p < PW[2] ? 1 : p < PW[3] ? 2 : 3;
+            const int o = p - (L == 1 ? PW[1] : L == 2 ? PW[2] : PW[3]), out = L == 3 ? OUT[3] : OUT[1];
+            store_param_bf(img, L, o / out, o % out, w);
+        }
+    }
+}
+
+template <bool BF>
 __global__ __launch_bounds__(256) void pack_kernel(const float* params, float* img) {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < P_REF) store_param(img, param_index(p), params[p]);
+    if (p < P_REF) store_param<BF>(img, p, param_index(p), params[p]);
 }
 
 // ctl: [0] optimiser steps S, [1] beta1^S, [2] beta2^S (f32 bits); [4..6] the training
@@ -496,6 +533,7 @@ struct AdamArgs {
 constexpr int ADAM_BLOCK = 256;
 constexpr int ADAM_GRID = (P_REF + N_MET + ADAM_BLOCK - 1) / ADAM_BLOCK;
 
+template <bool BF>
 __global__ __launch_bounds__(ADAM_BLOCK) void reduce_adam_kernel(AdamArgs a) {
     const int p = blockIdx.x * ADAM_BLOCK + threadIdx.x;
     const uint32_t S = a.ctl[4];
@@ -530,7 +568,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void reduce_adam_kernel(AdamArgs a) {
             a.v[p] = v;
             const float w = a.params[p] - rd::adam_delta(m, v, alpha, a.eps);
             a.params[p] = w;
-            store_param(a.img, ix, w);
+            store_param<BF>(a.img, p, ix, w);
         }
     }
     if (a.adam && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -556,7 +594,8 @@ struct rdm_trainer {
     int grid = 0;               // workspace rows
     int last_grid = 0;          // workgroups of the last training launch
     float* params = nullptr;    // [P_REF] f32 master
-    float* img = nullptr;       // [IMG] weight image (forward + backward layouts)
+    float* img = nullptr;       // [IMG_ALL] weight image (forward + backward layouts; f32, then bf16)
+    bool bf = false;            // rdm_create_dtype's RDM_DTYPE_BF16: the BF = true instances of every kernel
     float* m = nullptr;
     float* v = nullptr;
     float* grad = nullptr;
@@ -615,10 +654,14 @@ int launch_train(rdm_trainer* t, const float* x, const float* tgt, int64_t n, in
     const int rows = small ? 16 : 64;
     const int64_t nblk = (n + rows - 1) / rows;
     t->last_grid = (int)(nblk < t->grid ? nblk : t->grid);
-    if (small)
-        hipLaunchKernelGGL((student_mlp_kernel<true, 16>), dim3(t->last_grid), dim3(BLOCK), 0, t->stream, a);
+    const dim3 grid(t->last_grid), block(BLOCK);
+    if (t->bf) {
+        if (small) hipLaunchKernelGGL((student_mlp_kernel<true, 16, true>), grid, block, 0, t->stream, a);
+        else hipLaunchKernelGGL((student_mlp_kernel<true, 64, true>), grid, block, 0, t->stream, a);
+    } else if (small)
+        hipLaunchKernelGGL((student_mlp_kernel<true, 16, false>), grid, block, 0, t->stream, a);
     else
-        hipLaunchKernelGGL((student_mlp_kernel<true, 64>), dim3(t->last_grid), dim3(BLOCK), 0, t->stream, a);
+        hipLaunchKernelGGL((student_mlp_kernel<true, 64, false>), grid, block, 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_kernel launch");
     return RD_OK;
 }
@@ -641,7 +684,8 @@ int launch_adam(rdm_trainer* t, int reduce, int adam) {
     a.b1 = t->cfg.beta1;
     a.b2 = t->cfg.beta2;
     a.eps = t->cfg.eps;
-    hipLaunchKernelGGL(reduce_adam_kernel, dim3(ADAM_GRID), dim3(ADAM_BLOCK), 0, t->stream, a);
+    if (t->bf) hipLaunchKernelGGL(reduce_adam_kernel<true>, dim3(ADAM_GRID), dim3(ADAM_BLOCK), 0, t->stream, a);
+    else hipLaunchKernelGGL(reduce_adam_kernel<false>, dim3(ADAM_GRID), dim3(ADAM_BLOCK), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp reduce_adam_kernel launch");
     return RD_OK;
 }
@@ -695,10 +739,13 @@ int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdfl
     const int64_t nblk = (a.n + rows - 1) / rows;
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(small ? ELay<16>::THREADS : ELay<64>::THREADS);
     const bool stu = act_with == RDM_ACT_STUDENT;
-    if (small && stu) hipLaunchKernelGGL((student_mlp_envs_kernel<16, true>), grid, block, 0, t->stream, a);
-    else if (small) hipLaunchKernelGGL((student_mlp_envs_kernel<16, false>), grid, block, 0, t->stream, a);
-    else if (stu) hipLaunchKernelGGL((student_mlp_envs_kernel<64, true>), grid, block, 0, t->stream, a);
-    else hipLaunchKernelGGL((student_mlp_envs_kernel<64, false>), grid, block, 0, t->stream, a);
+    // the teacher-acts instances run no student layer: one arithmetic
+    if (small && stu && t->bf) hipLaunchKernelGGL((student_mlp_envs_kernel<16, true, true>), grid, block, 0, t->stream, a);
+    else if (stu && t->bf) hipLaunchKernelGGL((student_mlp_envs_kernel<64, true, true>), grid, block, 0, t->stream, a);
+    else if (small && stu) hipLaunchKernelGGL((student_mlp_envs_kernel<16, true, false>), grid, block, 0, t->stream, a);
+    else if (small) hipLaunchKernelGGL((student_mlp_envs_kernel<16, false, false>), grid, block, 0, t->stream, a);
+    else if (stu) hipLaunchKernelGGL((student_mlp_envs_kernel<64, true, false>), grid, block, 0, t->stream, a);
+    else hipLaunchKernelGGL((student_mlp_envs_kernel<64, false, false>), grid, block, 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_envs_kernel launch");
     return RD_OK;
 }
@@ -722,15 +769,22 @@ extern "C" {
 int rdm_param_count(void) { return P_REF; }
 
 int rdm_create(rdm_trainer** out, const rdm_config* cfg, int device, void* hip_stream) {
+    return rdm_create_dtype(out, cfg, RDM_DTYPE_F32, device, hip_stream);
+}
+
+int rdm_create_dtype(rdm_trainer** out, const rdm_config* cfg, int32_t dtype, int device, void* hip_stream) {
     if (!out || !cfg) return rd::set_error(RD_EINVAL, "rdm_create: null argument");
     if ((cfg->loss != RDM_LOSS_MSE && cfg->loss != RDM_LOSS_KL) || !(cfg->lr > 0) || cfg->grid < 0 ||
         cfg->metrics_len < 0 || !(cfg->keep_prob > 0.0f && cfg->keep_prob <= 1.0f) || cfg->row_base < 0)
         return rd::set_error(RD_EINVAL, "rdm_create: bad config");
+    if (dtype != RDM_DTYPE_F32 && dtype != RDM_DTYPE_BF16)
+        return rd::set_error(RD_EINVAL, "rdm_create_dtype: unknown dtype %d", (int)dtype);
     rd::DeviceGuard dg(device);
     RD_HIP(dg.err, "rdm_create: hipSetDevice");
     rdm_trainer* t = new (std::nothrow) rdm_trainer();
     if (!t) return rd::set_error(RD_EINVAL, "rdm_create: out of host memory");
     t->cfg = *cfg;
+    t->bf = dtype == RDM_DTYPE_BF16;
     if (t->cfg.metrics_len == 0) t->cfg.metrics_len = 4096;
     t->device = device;
     t->stream = (hipStream_t)hip_stream;
@@ -742,7 +796,7 @@ int rdm_create(rdm_trainer** out, const rdm_config* cfg, int device, void* hip_s
         if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, t->stream);
     };
     alloc((void**)&t->params, sizeof(float) * P_REF);
-    alloc((void**)&t->img, sizeof(float) * IMG);
+    alloc((void**)&t->img, sizeof(float) * IMG_ALL);
     alloc((void**)&t->m, sizeof(float) * P_REF);
     alloc((void**)&t->v, sizeof(float) * P_REF);
     alloc((void**)&t->own_grad, sizeof(float) * P_REF);
@@ -786,7 +840,9 @@ int rdm_set_params(rdm_trainer* t, const float* params) {
     RD_HIP(dg.err, "rdm_set_params");
     RD_HIP(hipMemcpyAsync(t->params, params, sizeof(float) * P_REF, hipMemcpyDeviceToDevice, t->stream),
            "rdm_set_params");
-    hipLaunchKernelGGL(pack_kernel, dim3((P_REF + 255) / 256), dim3(256), 0, t->stream, t->params, t->img);
+    const dim3 grid((P_REF + 255) / 256), block(256);
+    if (t->bf) hipLaunchKernelGGL(pack_kernel<true>, grid, block, 0, t->stream, t->params, t->img);
+    else hipLaunchKernelGGL(pack_kernel<false>, grid, block, 0, t->stream, t->params, t->img);
     RD_HIP(hipGetLastError(), "rdm_set_params: pack");
     return RD_OK;
 }
@@ -831,10 +887,13 @@ int rdm_forward(rdm_trainer* t, const float* x, int64_t n, float* pdflat) {
     const int rows = small ? 16 : 64;
     const int64_t nblk = (n + rows - 1) / rows;
     const int grid = (int)(nblk < t->grid ? nblk : t->grid);
-    if (small)
-        hipLaunchKernelGGL((student_mlp_kernel<false, 16>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
+    if (t->bf) {
+        if (small) hipLaunchKernelGGL((student_mlp_kernel<false, 16, true>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
+        else hipLaunchKernelGGL((student_mlp_kernel<false, 64, true>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
+    } else if (small)
+        hipLaunchKernelGGL((student_mlp_kernel<false, 16, false>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
     else
-        hipLaunchKernelGGL((student_mlp_kernel<false, 64>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
+        hipLaunchKernelGGL((student_mlp_kernel<false, 64, false>), dim3(grid), dim3(BLOCK), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_kernel (forward) launch");
     return RD_OK;
 }
@@ -947,10 +1006,11 @@ int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, flo
     const int rows = small ? 16 : 64;
     const int64_t nblk = (a.n + rows - 1) / rows;
     const int grid = (int)(nblk < cap ? nblk : cap);
-    if (small)
-        hipLaunchKernelGGL(student_mlp_evaluate_kernel<16>, dim3(grid), dim3(ELay<16>::THREADS), 0, t->stream, a);
-    else
-        hipLaunchKernelGGL(student_mlp_evaluate_kernel<64>, dim3(grid), dim3(ELay<64>::THREADS), 0, t->stream, a);
+    const dim3 blocks(grid), threads(small ? ELay<16>::THREADS : ELay<64>::THREADS);
+    if (small && t->bf) hipLaunchKernelGGL((student_mlp_evaluate_kernel<16, true>), blocks, threads, 0, t->stream, a);
+    else if (t->bf) hipLaunchKernelGGL((student_mlp_evaluate_kernel<64, true>), blocks, threads, 0, t->stream, a);
+    else if (small) hipLaunchKernelGGL((student_mlp_evaluate_kernel<16, false>), blocks, threads, 0, t->stream, a);
+    else hipLaunchKernelGGL((student_mlp_evaluate_kernel<64, false>), blocks, threads, 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
     return RD_OK;
 }

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs 
     a.clock[a.n + i] = 0;
 }
 
-template <int ROWS, bool STUDENT_ACTS>
+template <int ROWS, bool STUDENT_ACTS, bool BF>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(SmEnvsArgs a) {
     using LY = Lay<ROWS>;
     using EL = ELay<ROWS>;
@@ -118,16 +118,16 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(S
             }
             __syncthreads();
             if constexpr (STUDENT_ACTS) {
-                if (student) fwd_layer<RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
                 __syncthreads();
                 // fenced: in the 64-env instance hipcc loaded layer 1's next weights into the bias quad its
                 // four row blocks' first MFMAs share as SrcC (hazards.py LDSRC).  Fencing every layer
                 // scans clean too and costs 2-3 % of the launch (profiles/student_mlp_envs_fence_ab.txt)
-                if (student) fwd_layer<RB, 1, S_X1, S_X2, true>(X1, X2, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 1, S_X1, S_X2, true>(X1, X2, a.img, wave, i, g);
                 __syncthreads();
             }
             if (student) {
-                if constexpr (STUDENT_ACTS) fwd_layer<RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
+                if constexpr (STUDENT_ACTS) fwd<BF, RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
             } else {   // the teacher on tile wave - 8, beside the student's largest layer
                 const int t = wave - WAVES;
                 f32x4 H1[4], H2[4];
@@ -140,9 +140,9 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(S
             }
             __syncthreads();
             if constexpr (STUDENT_ACTS) {
-                if (student) fwd_layer<RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
                 __syncthreads();
-                if (student) fwd_layer<RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
                 __syncthreads();
             }
             // the next step's first writes (X0, SO) follow every read of them: X0's before the

@@ -51,7 +51,7 @@ struct SmEvalArgs {
     int episodes, first_episode;
 };
 
-template <int ROWS>
+template <int ROWS, bool BF>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kernel(SmEvalArgs a) {
     using LY = Lay<ROWS>;
     using EL = ELay<ROWS>;
@@ -114,12 +114,12 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                     prev_field = carry;
                 }
                 __syncthreads();
-                if (student) fwd_layer<RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 0, S_X0, S_X1>(X0, X1, a.img, wave, i, g);
                 __syncthreads();
-                if (student) fwd_layer<RB, 1, S_X1, S_X2>(X1, X2, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 1, S_X1, S_X2>(X1, X2, a.img, wave, i, g);
                 __syncthreads();
                 if (student) {
-                    fwd_layer<RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
+                    fwd<BF, RB, 2, S_X2, S_X3>(X2, X3, a.img, wave, i, g);
                 } else {   // the teacher on tile wave - 8, beside the student's largest layer
                     const int t = wave - WAVES;
                     f32x4 H1[4], H2[4];
@@ -131,9 +131,9 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                     }
                 }
                 __syncthreads();
-                if (student) fwd_layer<RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 3, S_X3, S_X4>(X3, X4, a.img, wave, i, g);
                 __syncthreads();
-                if (student) fwd_layer<RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
+                if (student) fwd<BF, RB, 4, S_X4, S_D5>(X4, D5, a.img, wave, i, g);
                 __syncthreads();
                 // the next step's first writes (X0, SO) follow every read of them: X0's before the
                 // second barrier above, SO's before the fourth

@@ -43,7 +43,7 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
           loss: str = "kl", lr: float = 1e-4, seed: int = 0, device="cuda:0", teacher_path: str | None = None,
           warmup_episodes: int = 2 * MLP_BATCH_SIZE, student: str = "policy", keep_prob: float = 1.0,
           log=print, gym_env: bool = False, store_dir: str | None = None, pool: str = "reference",
-          stop_loss: float | None = None, teacher=None):
+          stop_loss: float | None = None, teacher=None, dtype: str = "f32"):
     """Returns (trainer, dataset, per-episode summed training loss); the trainer is the
     DistillTrainer (student="policy") or the StudentMlpTrainer (student="mlp").  The env I/O
     stays on the device (driver_env.DriverEnv; gym_env=True: through the gym-API env, numpy
@@ -53,14 +53,18 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
     stored pages join the training pool (dataset.py:164-177); ``pool="ring"`` draws windows
     uniformly from the device ring instead.  ``stop_loss``: also stop after the first DAgger
     episode whose mean window loss falls below it (convergence measurements).  ``teacher``: an
-    MlpPolicyParams used instead of the restored / synthetic one (e.g. teacher.fit_teacher)."""
+    MlpPolicyParams used instead of the restored / synthetic one (e.g. teacher.fit_teacher).
+    ``dtype``: the arithmetic of the student="mlp" trainer (StudentMlpConfig.dtype: "f32", or "bf16"
+    mixed precision, in which the student that acts is the student that is trained)."""
     if student not in ("policy", "mlp"):
         raise ValueError(f"unknown student {student!r}")
     env = DriverEnv(seed, device, gym_api=gym_env)
     pi = teacher if teacher is not None else \
         TeacherAgent(restore=teacher_path is not None, path=teacher_path).pi   # always restored (ref. :29)
     tr = DistillTrainer(DistillConfig(n_envs=64, seed=seed, loss=loss, lr=lr), device=device, teacher=pi)
-    sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed),
+    if student != "mlp" and dtype != "f32":
+        raise ValueError('dtype selects the arithmetic of student="mlp" only')
+    sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, dtype=dtype),
                            device=device) if student == "mlp" else None
     dataset = DeviceDataset(device=device, seed=seed, store=PageStore(store_dir) if store_dir else None, pool=pool)
     ob = env.reset()                                  # [1, 11] on the device
@@ -115,7 +119,7 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
 # -- the reference student distilled on-policy over many envs ----------------------------------
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-4,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
-               eval_every: int = 0, eval_envs: int = 4096):
+               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32"):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -129,13 +133,15 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     the mean over rows and both action dims against the teacher, the reward the mean over the
     batch's env steps.  With ``eval_every`` > 0 returns (trainer, history, evals): evals rows
     (optimiser step, mean return of StudentMlpTrainer.evaluate over ``eval_envs`` fresh envs, one
-    episode) after every eval_every-th step -- the reference's average reward per keep_prob."""
+    episode) after every eval_every-th step -- the reference's average reward per keep_prob.
+    ``dtype``: StudentMlpConfig.dtype ("bf16": mixed precision in the env, training and evaluation
+    launches alike)."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
         raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
-    sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, metrics_len=steps),
-                           device=device)
+    sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, metrics_len=steps,
+                                            dtype=dtype), device=device)
     sm.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     sm.attach_envs(n, seed=seed, accum_steps=K)
     rew = torch.zeros(steps, device=sm.device)

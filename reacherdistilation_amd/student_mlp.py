@@ -31,6 +31,7 @@ DIMS = (16, 24, 128, 128, 32, 4)          # student_nn.py:51-57
 N_PARAMS = sum(a * b + b for a, b in zip(DIMS[:-1], DIMS[1:]))   # 24,380
 IN_DIM = OBSPACE_SHAPE + PDFLAT_SHAPE + 1
 LOSSES = {"mse": 0, "kl": 1}
+DTYPES = {"f32": 0, "bf16": 1}            # RDM_DTYPE_*
 
 
 class RdmConfig(ctypes.Structure):
@@ -61,6 +62,7 @@ nat.register({
     "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
     "rdm_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdmConfig), INT, P]),
+    "rdm_create_dtype": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdmConfig), I32, INT, P]),
     "rdm_destroy": (INT, [P]),
     "rdm_set_stream": (INT, [P, P]),
     "rdm_set_params": (INT, [P, P]),
@@ -117,6 +119,21 @@ class StudentMlpConfig:
     init_seed: int = 2
     grid: int = 0
     metrics_len: int = 4096
+    dtype: str = "f32"          # "bf16": layers 1-3 on the bf16 matrix path, f32 master and sums
+                                # (reacher_student_mlp.h "Arithmetic"), in every call of the trainer
+
+    def __post_init__(self):
+        if self.dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(DTYPES)}, got {self.dtype!r}")
+
+    def native(self, row_base: int = 0):
+        """(rdm_config, RDM_DTYPE_*): what rdm_create_dtype takes."""
+        if self.dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(DTYPES)}, got {self.dtype!r}")
+        c = RdmConfig(loss=LOSSES[self.loss], lr=self.lr, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                      grid=self.grid, metrics_len=self.metrics_len, keep_prob=self.keep_prob,
+                      seed=self.seed % 2 ** 64, row_base=int(row_base))
+        return c, DTYPES[self.dtype]
 
 
 class StudentMlpTrainer:
@@ -127,15 +144,13 @@ class StudentMlpTrainer:
         if self.device.type != "cuda":
             raise ValueError("StudentMlpTrainer runs on a GPU (HIP) device only; there is no CPU path")
         self.rank, self.world, self.pg = rank, world_size, process_group
+        c, dtype = self.cfg.native(row_base)   # a bad dtype raises before any native call
         self._lib = nat.load()
         assert self._lib.rdm_param_count() == N_PARAMS
-        c = RdmConfig(loss=LOSSES[self.cfg.loss], lr=self.cfg.lr, beta1=self.cfg.beta1, beta2=self.cfg.beta2,
-                      eps=self.cfg.eps, grid=self.cfg.grid, metrics_len=self.cfg.metrics_len,
-                      keep_prob=self.cfg.keep_prob, seed=self.cfg.seed % 2 ** 64, row_base=int(row_base))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(self._lib.rdm_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
-                                           nat.stream_handle(self.device)), "rdm_create")
+            nat.check(self._lib.rdm_create_dtype(ctypes.byref(h), ctypes.byref(c), dtype, self.device.index or 0,
+                                                 nat.stream_handle(self.device)), "rdm_create_dtype")
         self._h = h
         self.teacher = None   # the teacher of evaluate() and of the envs (set_teacher)
         self.n_envs, self.accum_steps, self._envs = 0, 0, None   # attach_envs
