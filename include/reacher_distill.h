@@ -231,6 +231,12 @@ int rdd_set_env_state(rdd_trainer* tr, const float* state);
 int rdd_get_counter(rdd_trainer* tr, int64_t* steps);              /* env steps */
 int rdd_get_counters(rdd_trainer* tr, int64_t* env_steps, int64_t* opt_steps);
 int rdd_read_metrics(rdd_trainer* tr, int64_t count, double* out);
+/* The layout launch_rollout chose for the trainer's last rollout launch (env, obs or rows):
+ * out[0] = envs/rows per group (16|32|64), out[1] = workgroups, out[2] = 1 if the helper-pair
+ * kernel ran, out[3] = 0 env / 1 obs / 2 rows.  Host-only, no device call, no sync.  Before the
+ * first launch: the env rollout's group size and grid, out[2] = out[3] = 0.
+ * RD_EINVAL: NULL trainer or out. */
+int rdd_last_layout(const rdd_trainer* tr, int32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,7 @@ struct rdd_trainer {
     uint32_t* ctl = nullptr;   // [16]: step words, snapshot, [8] hand-off timeout flag
     unsigned long long* dbg = nullptr;   // RD_STAMPS builds only
     int last_grid = 0;                   // workgroups of the last rollout (rows of ws to reduce)
+    int last_gs = GROUP, last_hlp = 0, last_mode = 0;   // ... its group size, helper layout, 0 env / 1 obs / 2 rows
     int ws_rows = 0;                     // rows of ws (the device's CU count, or cfg.grid)
     int cus = 0;                         // the device's CU count (rdd_evaluate's grid: no query per launch)
     int gs = GROUP;                      // envs per group of the env rollout
@@ -200,6 +201,9 @@ int launch_rollout(rdd_trainer* t, const float* obs_in = nullptr, int64_t n_obs 
                      ksteps == 1;                // K env steps per launch: the plain layout
     if (hlp) grid = (int)((ngroups + 1) / 2);
     t->last_grid = grid;
+    t->last_gs = a.gs;
+    t->last_hlp = hlp;
+    t->last_mode = tflat_in ? 2 : (obs_in ? 1 : 0);
     void (*k)(RolloutArgs) =
         bs ? (spl ? rollout_kernel<true, true, true, MD_TEACHER, false, true>   // TC: DESIGN.md §3 "c5"
                   : rollout_kernel<true, false, true, MD_TEACHER>)
@@ -262,6 +266,7 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
     t->gs = group_envs(cfg->n_envs, cap * PAIRS, cfg->group_envs);
     t->grid = grid_for(cfg->n_envs, t->gs, cap);
     t->last_grid = t->grid;
+    t->last_gs = t->gs;
     const size_t netf = P_TOT + 2 * OBD;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) {
@@ -610,6 +615,15 @@ int rdd_read_metrics(rdd_trainer* t, int64_t count, double* out) {
         for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
     }
     delete[] host;
+    return RD_OK;
+}
+
+int rdd_last_layout(const rdd_trainer* t, int32_t out[4]) {
+    if (!t || !out) return rd::set_error(RD_EINVAL, "rdd_last_layout: null argument");
+    out[0] = t->last_gs;
+    out[1] = t->last_grid;
+    out[2] = t->last_hlp;
+    out[3] = t->last_mode;
     return RD_OK;
 }
 

@@ -80,6 +80,7 @@ nat.register({
     "rdd_rollout_rows": (INT, [P, P, P, I64, I64]),
     "rdd_step_rows": (INT, [P, P, P, I64]),
     "rdd_read_metrics": (INT, [P, I64, P]),
+    "rdd_last_layout": (INT, [P, ctypes.POINTER(I32)]),
     "rdd_bind_comm": (INT, [P, P]),
     "rdd_allreduce_grad": (INT, [P]),
 })
@@ -246,6 +247,7 @@ class DistillTrainer:
             self.allreduce_grad()
             nat.check(self._lib.rdd_apply(self._h), "rdd_apply")
         self._keep = obs   # the launch reads it asynchronously
+        self.steps += 1   # one optimiser step, as step_rows()
 
     def rollout_obs(self, obs: torch.Tensor, n_global: int | None = None):
         obs = self._obs_arg(obs)
@@ -294,6 +296,13 @@ class DistillTrainer:
         e, o = ctypes.c_int64(), ctypes.c_int64()
         nat.check(self._lib.rdd_get_counters(self._h, ctypes.byref(e), ctypes.byref(o)), "rdd_get_counters")
         return e.value, o.value
+
+    def last_layout(self):
+        """(rows per group, workgroups, helper-pair kernel, mode) of the last rollout launch
+        (rdd_last_layout); mode is "env", "obs" or "rows".  Host-only."""
+        out = (I32 * 4)()
+        nat.check(self._lib.rdd_last_layout(self._h, out), "rdd_last_layout")
+        return out[0], out[1], bool(out[2]), ("env", "obs", "rows")[out[3]]
 
     def set_stream(self, stream: torch.cuda.Stream):
         nat.check(self._lib.rdd_set_stream(self._h, ctypes.c_void_p(stream.cuda_stream)), "rdd_set_stream")

@@ -113,3 +113,53 @@ def test_state_check_rejects_one_wrong_velocity():
         bad[3, e] += 1e-4
         assert not parity.state_ok(bad, ref, active)[0]
         assert np.isclose(bad, ref, atol=3e-4, rtol=1e-4).all()
+
+
+# ---------------------------------------------------------------- caller batches (obs / rows mode)
+@pytest.mark.parametrize("n", [17, 203, 499, 1000])
+@pytest.mark.parametrize("loss", ["mse", "kl"])
+@pytest.mark.parametrize("mode", ["obs", "rows"])
+def test_caller_batch_checks_reject_a_lost_or_doubled_row(mode, n, loss):
+    """The ragged shapes of tests/test_caller_batch_gpu.py, with its inputs and tolerances: the
+    oracle gradient carried through f32 passes; with the last row dropped, with the rows of the
+    last (ragged) 16-row tile dropped, and with the first row of the last group counted twice,
+    parity.grad_ok rejects it."""
+    from tests import caller_batch as cb
+    ob, t = cb.batch(n)
+    g64, M, _, _ = cb.reference(mode, n, loss)
+    ok, rep = parity.grad_ok(g64.astype(np.float32), g64, M)
+    assert ok, rep
+    gs = cb.LAYOUTS[n][mode == "rows"][0]
+    tile0, group0 = (n - 1) // 16 * 16, (n - 1) // gs * gs
+    assert tile0 < n and (n - tile0) < 16 and group0 <= tile0        # the last tile is ragged
+    for what, delta in (("last row", -cb.row_contributions(mode, ob, t, loss, n, [n - 1])),
+                        ("last tile", -cb.row_contributions(mode, ob, t, loss, n, list(range(tile0, n)))),
+                        ("doubled row", cb.row_contributions(mode, ob, t, loss, n, [group0]))):
+        ok, rep = parity.grad_ok((g64 + delta).astype(np.float32), g64, M)
+        assert not ok, (what, rep)
+
+
+def test_caller_batch_row_contributions_sum_to_the_gradient():
+    """The mutations above are built from row_contributions: over all rows it is the oracle
+    gradient itself (both modes, KL with its per-row log-std term)."""
+    from tests import caller_batch as cb
+    n = 203
+    ob, t = cb.batch(n)
+    for mode in ("obs", "rows"):
+        for loss in ("mse", "kl"):
+            g64 = cb.reference(mode, n, loss)[0]
+            c = cb.row_contributions(mode, ob, t, loss, n, list(range(n)))
+            assert np.abs(c - g64).max() <= 1e-12 * np.abs(g64).max()
+
+
+def test_caller_batch_inputs_reach_the_clip_and_the_table_matches_the_layout_constants():
+    from tests import caller_batch as cb
+    teacher, student = cb.nets()
+    for n in (17, 203):
+        assert cb.clipped(cb.batch(n)[0], teacher) > 0 and cb.clipped(cb.batch(n)[0], student) > 0
+    # the single row of the n = 1 cases: resolvable by f32 arithmetic (tests/caller_batch.py), and a
+    # typical row is not (which is why it is chosen)
+    assert cb.single_row_ok(cb.SINGLE_ROW_SEED)
+    assert not any(cb.single_row_ok(s) for s in range(1, cb.SINGLE_ROW_SEED))
+    c = cb.layout_constants()
+    assert c == {"WAVES": 8, "GROUP": 64, "TILE": 16}, c   # else: derive tests/caller_batch.py LAYOUTS again
