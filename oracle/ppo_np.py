@@ -124,8 +124,10 @@ def standardize(adv):
     return (adv - adv.mean()) / adv.std()
 
 
-def loss_and_grads(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
-    """Minibatch loss terms and the gradient of pol_surr + vf_loss w.r.t. [pol | vf]."""
+def _rows(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
+    """Per-row terms of the minibatch loss: forwards, ratio, the min / clip branch masks (TF's
+    conventions) and the head derivatives dlp = d loss / d logp, dv = d loss / d v, both with
+    the divisor n."""
     n = z.shape[0]
     fp, fv = pol_forward(pol, z), vf_forward(vf, z)
     lp = logp(fp["mean"], fp["logstd"], a)
@@ -133,40 +135,73 @@ def loss_and_grads(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
     s1 = ratio * atarg
     rc = np.clip(ratio, 1.0 - clip_eps, 1.0 + clip_eps)
     s2 = rc * atarg
-    pol_surr = -np.minimum(s1, s2).mean()
-    vf_loss = np.square(fv["v"] - ret).mean()
     # d(-min)/dratio with TF's conventions
     take1 = s1 <= s2
     inside = (ratio >= 1.0 - clip_eps) & (ratio <= 1.0 + clip_eps)
     dr = np.where(take1, -atarg, np.where(inside, -atarg, 0.0)) / n
-    dlp = dr * ratio
     std = np.exp(fp["logstd"])
-    dmean = dlp[:, None] * (a - fp["mean"]) / std ** 2
-    dls = (dlp[:, None] * (((a - fp["mean"]) / std) ** 2 - 1.0)).sum(0)
-    W1, b1, W2, b2, W3, b3, _ = unpack_pol(pol)
-    gW3 = fp["h2"].T @ dmean
-    gb3 = dmean.sum(0)
-    d2 = (dmean @ W3.T) * (1 - fp["h2"] ** 2)
-    gW2 = fp["h1"].T @ d2
+    return dict(fp=fp, fv=fv, ratio=ratio, s1=s1, s2=s2, live=take1 | inside, dlp=dr * ratio,
+                x=(a - fp["mean"]) / std, std=std, dv=2.0 * (fv["v"] - ret)[:, None] / n)
+
+
+def _net_backward(W2, W3, h1, h2, z, dtop):
+    """Weight / bias gradients of a 2 x 64 tanh net with a dense head from d loss / d head
+    output dtop [n, k], in layout order W1 b1 W2 b2 W3 b3."""
+    g3 = h2.T @ dtop
+    gb3 = dtop.sum(0)
+    d2 = (dtop @ W3.T) * (1 - h2 ** 2)
+    g2 = h1.T @ d2
     gb2 = d2.sum(0)
-    d1 = (d2 @ W2.T) * (1 - fp["h1"] ** 2)
-    gW1 = z.T @ d1
+    d1 = (d2 @ W2.T) * (1 - h1 ** 2)
+    g1 = z.T @ d1
     gb1 = d1.sum(0)
-    gpol = np.concatenate([gW1.ravel(), gb1, gW2.ravel(), gb2, gW3.ravel(), gb3, dls])
-    V1, c1, V2, c2, V3, c3 = unpack_vf(vf)
-    dv = 2.0 * (fv["v"] - ret)[:, None] / n
-    gV3 = fv["g2"].T @ dv
-    gc3 = dv.sum(0)
-    e2 = (dv @ V3.T) * (1 - fv["g2"] ** 2)
-    gV2 = fv["g1"].T @ e2
-    gc2 = e2.sum(0)
-    e1 = (e2 @ V2.T) * (1 - fv["g1"] ** 2)
-    gV1 = z.T @ e1
-    gc1 = e1.sum(0)
-    gvf = np.concatenate([gV1.ravel(), gc1, gV2.ravel(), gc2, gV3.ravel(), gc3])
-    ent = (fp["logstd"] + 0.5 * np.log(2 * np.pi * np.e)).sum()
+    return [g1.ravel(), gb1, g2.ravel(), gb2, g3.ravel(), gb3]
+
+
+def _grads(pol, vf, z, t, rows=slice(None), absolute=False, dlp=None):
+    """(gpol, gvf) from the per-row terms t of _rows over `rows`; absolute: every factor replaced
+    by its absolute value (1 - h^2 is unchanged by it); dlp: overrides t["dlp"]."""
+    f = np.abs if absolute else (lambda v: v)
+    dlp = (t["dlp"] if dlp is None else dlp)[rows]
+    x = t["x"][rows]
+    dmean = f(dlp)[:, None] * f(x) / t["std"]
+    dls = (f(dlp)[:, None] * f(x ** 2 - 1.0)).sum(0)
+    _, _, W2, _, W3, _, _ = unpack_pol(pol)
+    fp, fv = t["fp"], t["fv"]
+    gpol = np.concatenate(_net_backward(f(W2), f(W3), f(fp["h1"][rows]), f(fp["h2"][rows]), f(z[rows]), dmean) + [dls])
+    _, _, V2, _, V3, _ = unpack_vf(vf)
+    gvf = np.concatenate(_net_backward(f(V2), f(V3), f(fv["g1"][rows]), f(fv["g2"][rows]), f(z[rows]), f(t["dv"][rows])))
+    return gpol, gvf
+
+
+def loss_and_grads(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
+    """Minibatch loss terms and the gradient of pol_surr + vf_loss w.r.t. [pol | vf]."""
+    t = _rows(pol, vf, z, a, logp_old, atarg, ret, clip_eps)
+    pol_surr = -np.minimum(t["s1"], t["s2"]).mean()
+    vf_loss = np.square(t["fv"]["v"] - ret).mean()
+    gpol, gvf = _grads(pol, vf, z, t)
+    ent = (t["fp"]["logstd"] + 0.5 * np.log(2 * np.pi * np.e)).sum()
     kl = None
-    return dict(pol_surr=pol_surr, vf_loss=vf_loss, ent=ent, gpol=gpol, gvf=gvf, ratio=ratio, kl=kl)
+    return dict(pol_surr=pol_surr, vf_loss=vf_loss, ent=ent, gpol=gpol, gvf=gvf, ratio=t["ratio"], kl=kl)
+
+
+def grad_scale(pol, vf, z, a, logp_old, atarg, ret, clip_eps):
+    """(M_pol, M_vf, live): M_e = sum over rows of |that row's contribution to gradient entry e|
+    (an upper bound of it: loss_and_grads' backward with every factor replaced by its absolute
+    value; the rows whose surrogate gradient is zero stay zero; the log-std entries are
+    sum |dlp| |x^2 - 1|), the natural scale of an f32 sum over the rows.  live: the rows the
+    policy gradient takes, take1 | inside."""
+    t = _rows(pol, vf, z, a, logp_old, atarg, ret, clip_eps)
+    M_pol, M_vf = _grads(pol, vf, z, t, absolute=True)
+    return M_pol, M_vf, t["live"]
+
+
+def row_contributions(pol, vf, z, a, logp_old, atarg, ret, clip_eps, rows, as_live=False):
+    """(gpol, gvf) restricted to `rows` of the minibatch, the divisor n kept: over all rows it is
+    loss_and_grads' gradient.  as_live: the rows' policy contribution as if none were dead."""
+    t = _rows(pol, vf, z, a, logp_old, atarg, ret, clip_eps)
+    dlp = -atarg / z.shape[0] * t["ratio"] if as_live else None
+    return _grads(pol, vf, z, t, rows=np.asarray(rows, np.int64), dlp=dlp)
 
 
 def mt19937_64(seed):

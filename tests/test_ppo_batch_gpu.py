@@ -5,7 +5,8 @@ oracle/ppo_np.py, the C oracle's env (oracle/ref_c.py) and policy_np.AdamTF1.
     value predictions, the bootstrap value, GAE, the filter and the metrics row, with env
     ids that cross 2^32, a seed with a high word, two logstd values and two GAE blocks;
   * shuffled minibatches: the gradient of the last minibatch of the last epoch is the
-    oracle's over the rows that oracle.ppo_np.shuffles names (and not over other rows);
+    oracle's over the rows that oracle.ppo_np.shuffles names (and not over other rows), by the
+    relative L2 norm of [pol | vf] and by tests/ppo_parity.py's bound on each net;
   * the Adam step (epsilon 1e-5, lr = stepsize * lrmult, beta powers carried across
     iterations), the schedule clamp and the constant schedule;
   * the clipped epoch's pol_surr, vf_loss and clipfrac;
@@ -23,6 +24,7 @@ from oracle import policy_np as pn
 from oracle import ppo_np as pp
 from oracle import ref_c
 from oracle.refnet_np import M32, philox4x32_10
+from tests import ppo_parity as par
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -245,6 +247,9 @@ def test_shuffled_minibatch_gradient_matches_oracle(n, T, mb, E, it):
 
     last = [oracle(perm[E - 1][j * mb:(j + 1) * mb]) for j in range(nmb)]
     assert rel(last[-1]) < 1e-3, rel(last[-1])
+    rows = perm[E - 1][(nmb - 1) * mb:nmb * mb]                      # each net at its own scale
+    par.check_grad(g, par.reference(pol, vf, z[rows], a[rows], lpo[rows], atarg[rows], ret[rows], eps),
+                   f"shuffled {n}x{T} mb {mb} epochs {E} it {it}")
     identity = np.arange((nmb - 1) * mb, nmb * mb)                   # the same slice without the shuffle
     assert not rel(oracle(identity)) < 1e-3, rel(oracle(identity))
     m = tr.metrics(1)[0]

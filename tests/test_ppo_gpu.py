@@ -4,8 +4,9 @@ The actor batch is checked record by record: value predictions (f32 MLP vs f64: 
 1e-4 rel), actions = mean + exp(logstd) * the Box-Muller normal of the documented Philox
 words (1e-5 + 1e-4 rel), rewards from the record's own observation (the stale-fingertip
 reward -|tip - target| - |a|^2, 1e-5), episode-start flags, GAE (1e-4 rel of max|adv|); the
-observation filter's moments; the full-batch minibatch gradient (relative L2 < 1e-3; ratios
-straddle the clip range after one update) and learning.
+observation filter's moments; the full-batch minibatch gradient (relative L2 < 1e-3 of [pol | vf],
+which the value net dominates, and tests/ppo_parity.py's bound on each net at its own scale;
+ratios straddle the clip range after one update) and learning.
 """
 import numpy as np
 import pytest
@@ -13,6 +14,7 @@ import torch
 
 from oracle import ppo_np as pp
 from oracle.refnet_np import M32, philox4x32_10
+from tests import ppo_parity as par
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -95,10 +97,12 @@ def test_full_batch_gradient_matches_oracle(n, T):
     tr.optimize()
     g = tr.grad().cpu().numpy().astype(np.float64)
     # first minibatch of the epoch: old == current parameters, ratio = 1 (inside the clip)
-    r = pp.loss_and_grads(pol, vf, z, a, lpo, atarg, b["ret"].reshape(-1), 0.2 * lrmult)
+    r = par.reference(pol, vf, z, a, lpo, atarg, b["ret"].reshape(-1), 0.2 * lrmult)
     want = np.concatenate([r["gpol"], r["gvf"]])
     rel = np.linalg.norm(g - want) / np.linalg.norm(want)
     assert rel < 1e-3, rel
+    assert not r["dead"].any()
+    par.check_grad(g, r, f"full batch {n}x{T}")
     m = tr.metrics(1)[0]
     assert abs(m[2] - r["pol_surr"]) < 1e-4 and abs(m[3] - r["vf_loss"]) <= 1e-4 * r["vf_loss"] + 1e-5
     assert m[6] == pytest.approx(lrmult, rel=1e-6)
@@ -126,12 +130,13 @@ def test_clipped_branch_gradient_matches_oracle():
     pol1, vf1 = tr1.policy().cpu().numpy(), tr1.value().cpu().numpy()
     tr.optimize()
     g = tr.grad().cpu().numpy().astype(np.float64)
-    r = pp.loss_and_grads(pol1, vf1, z, a, lpo, atarg, b["ret"].reshape(-1), 0.2 * (1.0 - tr.S / 10 ** 6))
+    r = par.reference(pol1, vf1, z, a, lpo, atarg, b["ret"].reshape(-1), 0.2 * (1.0 - tr.S / 10 ** 6))
     clipped = np.abs(r["ratio"] - 1) > 0.2 * (1.0 - tr.S / 10 ** 6)
     assert clipped.any()
     want = np.concatenate([r["gpol"], r["gvf"]])
     rel = np.linalg.norm(g - want) / np.linalg.norm(want)
     assert rel < 2e-3, rel
+    par.check_grad(g, r, "clipped branch 256x64")
 
 
 def test_ppo_improves_the_return():

@@ -56,6 +56,65 @@ def test_gradient_matches_finite_differences(seed):
         assert abs(num - g[k]) <= 1e-6 + 1e-5 * abs(num), (k, num, g[k])
 
 
+@pytest.mark.parametrize("seed", [0, 1])
+def test_grad_scale_bounds_the_gradient_and_row_contributions_sum_to_it(seed):
+    """grad_scale's M is the backward on absolute values: M >= |g| entrywise, for both nets and
+    with dead rows in the batch; row_contributions over all rows is the gradient itself, over a
+    subset it is the gradient of the batch with the other rows' head derivatives zeroed."""
+    pol, vf = _nets(seed)
+    n = 40
+    args = _batch(n, pol, seed + 5) + (0.2,)
+    r = pp.loss_and_grads(pol, vf, *args)
+    M_pol, M_vf, live = pp.grad_scale(pol, vf, *args)
+    assert 0 < live.sum() < n
+    outside = np.abs(r["ratio"] - 1) > 0.2
+    assert (live & outside).any() and not (~live & ~outside).any()      # dead rows are outside the range
+    assert (M_pol >= np.abs(r["gpol"])).all() and (M_vf >= np.abs(r["gvf"])).all()
+    assert (M_pol > 0).all() and (M_vf > 0).all()
+    cp, cv = pp.row_contributions(pol, vf, *args, rows=np.arange(n))
+    assert np.abs(cp - r["gpol"]).max() <= 1e-12 * np.abs(r["gpol"]).max()
+    assert np.abs(cv - r["gvf"]).max() <= 1e-12 * np.abs(r["gvf"]).max()
+    sp, sv = np.zeros(pp.P_POL), np.zeros(pp.P_VF)
+    for i in range(n):
+        p, v = pp.row_contributions(pol, vf, *args, rows=[i])
+        assert (p == 0).all() == (not live[i]) and (v != 0).any()        # a dead row feeds the value net only
+        sp += p
+        sv += v
+    assert np.abs(sp - r["gpol"]).max() <= 1e-12 * np.abs(r["gpol"]).max()
+    assert np.abs(sv - r["gvf"]).max() <= 1e-12 * np.abs(r["gvf"]).max()
+    # as_live: the contribution a dead row would have, the clip ignored
+    dead = int(np.flatnonzero(~live)[0])
+    p, _ = pp.row_contributions(pol, vf, *args, rows=[dead], as_live=True)
+    assert (p != 0).any()
+    z, a, lpo, atarg, ret = args[:5]
+    free = pp.loss_and_grads(pol, vf, z, a, lpo, atarg, ret, 1e9)        # a range nothing leaves
+    q, _ = pp.row_contributions(pol, vf, z, a, lpo, atarg, ret, 1e9, rows=[dead])
+    assert np.array_equal(p, q) and free["ratio"][dead] == r["ratio"][dead]
+
+
+def test_grad_scale_is_zero_exactly_where_only_dead_rows_feed():
+    """Observation column 3 is non-zero on dead rows only: row 3 of dW1 is fed by dead rows alone,
+    so M and the gradient are exactly 0 there (policy net), while the value net, which has no dead
+    rows, keeps M > 0; every other entry of M_pol stays positive."""
+    pol, vf = _nets(2)
+    z, a, lpo, atarg, ret = _batch(40, pol, 9)
+    live = pp.grad_scale(pol, vf, z, a, lpo, atarg, ret, 0.2)[2]
+    assert 0 < live.sum() < 40
+    z[live, 3] = 0.0
+    fp = pp.pol_forward(pol, z)                          # keep every row's ratio: logp_old moves with logp
+    z0, _, lpo0, _, _ = _batch(40, pol, 9)
+    fp0 = pp.pol_forward(pol, z0)
+    lpo = lpo0 + pp.logp(fp["mean"], fp["logstd"], a) - pp.logp(fp0["mean"], fp0["logstd"], a)
+    r = pp.loss_and_grads(pol, vf, z, a, lpo, atarg, ret, 0.2)
+    M_pol, M_vf, live1 = pp.grad_scale(pol, vf, z, a, lpo, atarg, ret, 0.2)
+    np.testing.assert_array_equal(live1, live)
+    row3 = np.zeros(pp.P_POL, bool)
+    row3[3 * 64:4 * 64] = True
+    assert (M_pol[row3] == 0).all() and (r["gpol"][row3] == 0).all()
+    assert (M_pol[~row3] > 0).all()
+    assert (M_vf[3 * 64:4 * 64] > 0).all()
+
+
 def test_gae_matches_definition():
     rs = np.random.RandomState(2)
     T, N = 7, 3
