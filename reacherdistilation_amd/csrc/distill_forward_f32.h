@@ -1,7 +1,7 @@
 // distill.hip, part 2a: one net's exact-f32 forward on a 16-env tile and what it needs -- the SrcC
 // fence of a group of four f32 MFMAs, tanh4, the cross-lane sums, the store helpers, load_net and
-// mlp_forward.  Included by distill_forward.h, and by student_mlp_eval.h for the teacher of the
-// reference student's evaluation (one definition, two translation units).  Expects
+// mlp_forward.  Included by distill_forward.h, and by teacher_f32.h for the teacher inside the two
+// students' evaluation and envs kernels (one definition, three translation units).  Expects
 // distill_layout.h, rd_device.h's f32x4, mfma, ld4, kTanhScale, tanh_pre, and kFenceAll (true
 // only in distill.hip's -DRD_MFMA_SRCC_FENCE diagnostic build).
 #pragma once

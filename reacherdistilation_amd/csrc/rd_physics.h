@@ -20,7 +20,9 @@ namespace rd {
 // fuses into one FMA only inside one expression (clang fp contract "on"), never across
 // statements by the backend (-ffp-contract=fast-honor-pragmas, HIP's default).  So every kernel
 // that inlines the env step -- the fused rollout's K = 1 and K-step instances, the helper pairs,
-// the gym-API env kernel, PPO's rollout -- rounds it identically (bitwise the same states).
+// the gym-API env kernel, PPO's rollout, the teacher's and the two students' evaluation kernels,
+// the two students' persistent envs (the LSTM student's through envs_reset_one and env_time_limit
+// below) -- rounds it identically (bitwise the same states).
 #define FP_SOURCE_ROUNDING() _Pragma("clang fp contract(on)")
 
 // ------------------------------------------------------------------ constants
@@ -288,6 +290,42 @@ __device__ __forceinline__ void philox_draw(uint64_t seed, uint64_t env_id, uint
     d[3] = __fmaf_rn(0.01f, u01(o[3]), -0.005f);
     d[4] = __fmaf_rn(0.4f, u01(p[0]), -0.2f);
     d[5] = __fmaf_rn(0.4f, u01(p[1]), -0.2f);
+}
+
+// ------------------------------------------------------------------ envs a handle keeps on the device
+// (persistent envs: state [8][n], AUX rows of carried values [AUX][n], clock [2][n] = step of the
+// episode, episode.  student_lstm_envs.h calls these; student_mlp_envs.h has the same two bodies
+// written out: called through here its six kernel instances compile to the same instruction counts
+// in another order, and that translation unit's instruction text is kept as it was.)
+
+// rd_reset's arithmetic for env i: episode 0 from Philox(seed, env_base + i); aux rows and clock to 0
+template <int AUX>
+__device__ __forceinline__ void envs_reset_one(float* state, float* aux, int32_t* clock, int64_t n, int64_t i,
+                                               uint64_t seed, int64_t env_base) {
+    float d[6];
+    philox_draw(seed, (uint64_t)(env_base + i), 0u, d);
+    State st;
+    env_reset(st, d);
+    store_state(state, n, i, st);
+#pragma unroll
+    for (int k = 0; k < AUX; ++k) aux[k * n + i] = 0.0f;
+    clock[i] = 0;
+    clock[n + i] = 0;
+}
+
+// gym TimeLimit inside a step, as rd_step has it: the clock advances, and after its episode's last
+// step the env (of a thread that owns one) resets from Philox(seed, env_id, episode + 1)
+__device__ __forceinline__ void env_time_limit(State& st, int32_t& step, int32_t& episode, uint64_t seed,
+                                               uint64_t env_id, bool owns = true) {
+    if (++step == kEpisodeSteps) {
+        step = 0;
+        if (owns) {
+            float d[6];
+            ++episode;
+            philox_draw(seed, env_id, (uint32_t)episode, d);
+            env_reset(st, d);
+        }
+    }
 }
 
 }  // namespace rd

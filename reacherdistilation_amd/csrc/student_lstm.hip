@@ -1466,7 +1466,10 @@ __global__ void init_ctl_kernel(uint32_t* ctl, float b1, float b2) {
 
 constexpr int64_t SPLIT_FLOATS = 16 << 20;  // split-K partials (64 MB)
 
-// the whole-episode evaluation (rdl_evaluate): tch::, lstm_eval_pack_kernel, student_lstm_evaluate_kernel
+// one closed-loop step of a 16-env block, shared by the two below: tch::, the EV_* tiling,
+// lstm_eval_pack_kernel, the block's LDS and the ls_* pieces
+#include "student_lstm_query.h"
+// the whole-episode evaluation (rdl_evaluate): student_lstm_evaluate_kernel
 #include "student_lstm_eval.h"
 // the persistent envs (rdl_envs_*, rdl_rollout_envs, rdl_step_envs): LsEnvsArgs, student_lstm_envs_kernel
 #include "student_lstm_envs.h"

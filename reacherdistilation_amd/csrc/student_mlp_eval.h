@@ -16,14 +16,7 @@
 // rdm_forward on the assembled row, rd_step }, whatever ROWS and the grid.
 #pragma once
 
-// The 2x64 MlpPolicy's layouts and exact-f32 forward: the definitions distill.hip compiles, in a
-// namespace of their own (their WAVES, BLOCK, N_MET ... are not sm::'s).
-namespace tch {
-using rd::f32x4, rd::mfma, rd::ld4, rd::kTanhScale, rd::tanh_pre;
-constexpr bool kFenceAll = false;   // the all-fenced diagnostic build is distill.hip's; mlp_forward<true> is fenced
-#include "distill_layout.h"
-#include "distill_forward_f32.h"
-}  // namespace tch
+#include "teacher_f32.h"   // namespace tch: the teacher's layouts, load_net and mlp_forward
 
 constexpr int EREC = rd::kObsDim + 1 + 4 + 4 + 1;   // dataset.py's record: ob | reward | t_pdflat | s_pdflat | stepped_with
 static_assert(RDM_IN == rd::kObsDim + RDM_OUT + 1 && tch::OBD == rd::kObsDim, "row = ob | prev pdflat | prev reward");
