@@ -21,6 +21,33 @@
  * Loss: kl_loss summed over T and B (loss.py:3-13), or action-MSE over T x rows_global.
  * Optimiser: TF1 Adam (reference lr 1e-3, lstm_train.py:73-79).
  *
+ * Arithmetic.  RDL_DTYPE_F32 (rdl_create): every product on v_mfma_f32_16x16x4_f32, exact f32
+ * products and f32 sums.  RDL_DTYPE_BF16 (rdl_create_dtype) is mixed precision.  These stay f32:
+ * the master weights and the Adam slots; every bias; the prev_pdflat projection (Wp, bp); the gate
+ * nonlinearities; c and h, the stored gates and the cell's backward point-wise arithmetic; the five
+ * head layers of every step, forward and backward; the loss, dbl, dWp, dbp and every accumulation.
+ * The three products of the cell matrix Wl[243][800] (86 % of the multiply-adds per row) round their
+ * operands to bf16, to nearest even (v_cvt_pk_bf16_f32); products are exact, sums f32, bf() below:
+ *     forward  z_t         = bl + sum_k bf([x_t | h_{t-1}]_k) bf(Wl_kc)
+ *     dgrad    [dx_t | dh] = sum_c bf(dz_t,c) bf(Wl_kc)     (dx's columns 11..42 feed dWp, dbp; dh
+ *                                                            feeds step t-1)
+ *     wgrad    dWl         = sum_{t,rows} bf([x_t | h_{t-1}]) bf(dz_t),   dbl = sum dz_t (unrounded)
+ * dz_t comes from the f32 cell backward on the unrounded stored gates and c.  The handle keeps two
+ * bf16 images of Wl (the second transposed, for the dgrad), roundings of the master, re-formed on
+ * the stream and without allocation by rdl_create_dtype, rdl_set_params and every Adam step
+ * (rdl_apply, rdl_step, rdl_step_envs).  The weight gradient is split over the rows and summed in a
+ * fixed order from a workspace sized at create from max_windows: no floating-point atomics, no
+ * hand-off between workgroups, no allocation after create; a bf16 step is capturable.
+ * Which calls run it: the window passes -- rdl_forward, rdl_rollout / rdl_step and the training
+ * pass inside rdl_rollout_envs / rdl_step_envs.  A bf16 handle always takes the per-step recurrence
+ * path: the persistent kernels (at most 32 windows, latency bound) are f32 only and never launched
+ * by it, so RDL_KERNELS_STEP_RECURRENCE has no effect on it; RDL_KERNELS_LAYER_HEAD and
+ * rdl_head_path work as on an f32 handle (the head is f32 on either path).
+ * Which calls stay f32, on the master weights: the one-record-per-env query -- rdl_evaluate,
+ * rdl_envs_act and the act phase of rdl_rollout_envs / rdl_step_envs.  On a bf16 handle these are
+ * bitwise what an f32 handle with the same parameters returns (evaluate measures the checkpointed
+ * policy), and rdl_step_envs equals rdl_envs_act, then rdl_step (bf16) on the windows written.
+ *
  * Conventions as in reacher.h: device pointers, asynchronous on the handle's stream,
  * 0 = OK, RD_EINVAL, -(hipError_t).  Multi-GPU: windows sharded by the caller (row_base =
  * this rank's first global window); rdl_rollout, all-reduce(SUM) rdl_grad_buffer(), rdl_apply.
@@ -72,6 +99,12 @@ typedef struct rdl_trainer rdl_trainer;
 int64_t rdl_param_count(int32_t steps);
 /* the 'LSTM' scope: graph, kl_loss and Adam (lstm_train.py:35-79) */
 int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_stream);
+/* rdl_create with the arithmetic of the cell matrix's products chosen ("Arithmetic" above):
+ * rdl_create(cfg) == rdl_create_dtype(cfg, RDL_DTYPE_F32); any other dtype than these two is
+ * RD_EINVAL before any device call */
+#define RDL_DTYPE_F32 0
+#define RDL_DTYPE_BF16 1
+int rdl_create_dtype(rdl_trainer** out, const rdl_config* cfg, int32_t dtype, int device, void* hip_stream);
 int rdl_destroy(rdl_trainer* t);
 int rdl_set_stream(rdl_trainer* t, void* hip_stream);
 /* initialisation / saver.restore (lstm_train.py:82-107): params [RDL_PARAMS_T(steps)] */

@@ -21,6 +21,9 @@
 //    split-K with a fixed-order reduction when the output tile grid is small;
 //  * bias gradients are deterministic two-level column sums; no atomics anywhere.
 // Activations of all steps stay resident in HBM (sized at create for max_windows).
+// rdl_create_dtype's RDL_DTYPE_BF16 sends the three products of the cell matrix Wl (the gate product of
+// each step, input half included; dh / dP; dWl) to the bf16 MFMA kernels of student_lstm_bf16.h, always
+// on this per-step path; everything else, and an f32 handle, runs what is described above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1473,6 +1476,8 @@ constexpr int64_t SPLIT_FLOATS = 16 << 20;  // split-K partials (64 MB)
 #include "student_lstm_eval.h"
 // the persistent envs (rdl_envs_*, rdl_rollout_envs, rdl_step_envs): LsEnvsArgs, student_lstm_envs_kernel
 #include "student_lstm_envs.h"
+// the bf16 mixed-precision cell (rdl_create_dtype's RDL_DTYPE_BF16): the Wl images and the three MFMA kernels
+#include "student_lstm_bf16.h"
 
 }  // namespace
 
@@ -1511,6 +1516,11 @@ struct rdl_trainer {
     int64_t envs_n = 0, envs_base = 0;
     uint64_t envs_seed = 0;
     int envs_grid = 0;
+    // RDL_DTYPE_BF16 (student_lstm_bf16.h): the bf16 images of Wl (forward, then transposed) and the
+    // weight gradient's split-K partials [wsplits][243][800]; both null on an f32 handle
+    int dtype = RDL_DTYPE_F32;
+    bf16x8* wimg = nullptr;
+    float* wpart = nullptr;
 };
 
 namespace {
@@ -1584,8 +1594,19 @@ bool fused_head(const rdl_trainer* t, int64_t R) {
     return !(t->cfg.kernels & RDL_KERNELS_LAYER_HEAD) && t->hpart && R <= HF_MAX_ROWS;
 }
 
+bool bf16_cell(const rdl_trainer* t) { return t->dtype == RDL_DTYPE_BF16; }
+
 bool persistent(const rdl_trainer* t, int64_t B) {   // (T < PR_MAX_T: every phase fits its tag field)
-    return !(t->cfg.kernels & RDL_KERNELS_STEP_RECURRENCE) && B <= PR_ROWS && t->T < PR_MAX_T;
+    // a bf16 handle always takes the per-step path: the persistent kernels are f32 only
+    return !bf16_cell(t) && !(t->cfg.kernels & RDL_KERNELS_STEP_RECURRENCE) && B <= PR_ROWS && t->T < PR_MAX_T;
+}
+
+// the bf16 images of Wl from the master weights, on the stream (after every change of the master)
+int bf16_images(rdl_trainer* t) {
+    hipLaunchKernelGGL(lstm_bf16_image_kernel, dim3((BF_IMG_GROUPS + 255) / 256), dim3(256), 0, t->stream,
+                       (const float*)t->params, t->wimg);
+    RD_HIP(hipGetLastError(), "rdl lstm_bf16_image_kernel");
+    return RD_OK;
 }
 
 // forward over all T steps of B windows.  out_pdflat: where the head's output goes (the
@@ -1617,6 +1638,17 @@ int run_forward(rdl_trainer* t, const float* ob, const float* prev, const float*
         RDL_CK(hipMemsetAsync(t->Cs, 0, sizeof(float) * B * U, t->stream), "rdl state");
         RDL_CK(hipMemsetAsync(t->H, 0, sizeof(float) * B * U, t->stream), "rdl state");
     }
+    if (bf16_cell(t)) {   // both halves of the gate product in the step's launch, from the bf16 image
+        const dim3 grid((U / 16 + 4) / 4, (unsigned)((B + BF_ROWS - 1) / BF_ROWS));
+        for (int s = 0; s < T; ++s) {
+            hipLaunchKernelGGL(lstm_bf16_fwd_kernel, grid, dim3(256), 0, t->stream,
+                               (const float*)(t->X + (int64_t)s * B * XLD), (const float*)(t->H + (int64_t)s * B * U),
+                               (const float*)(t->Cs + (int64_t)s * B * U), (const bf16x8*)t->wimg, P + OFF_BL,
+                               t->G + (int64_t)s * B * G4, t->Cs + (int64_t)(s + 1) * B * U,
+                               t->H + (int64_t)(s + 1) * B * U, B);
+            RDL_CK(hipGetLastError(), "rdl lstm_bf16_fwd_kernel");
+        }
+    } else {
     // input half of the gate pre-activations for all steps: Z = X[:, :43] Wl[0:43] + bl
     RDL_CK(mm(t, (int)R, G4, XI, t->X, XLD, 0, P + OFF_WL, G4, 0, t->Z, G4, P + OFF_BL), "rdl gemm Zx");
     for (int s = 0; s < T; ++s) {
@@ -1626,6 +1658,7 @@ int run_forward(rdl_trainer* t, const float* ob, const float* prev, const float*
                            (const float*)Zs, (const float*)(t->Cs + (int64_t)s * B * U), t->G + (int64_t)s * B * G4,
                            t->Cs + (int64_t)(s + 1) * B * U, t->H + (int64_t)(s + 1) * B * U, B);
         RDL_CK(hipGetLastError(), "rdl lstm_rec_fwd_kernel");
+    }
     }
     }
     // step t's head over its B rows (student_nn.py:42-46, one head per unrolled step)
@@ -1746,6 +1779,29 @@ int run_backward(rdl_trainer* t, const float* prev, const float* tgt, int64_t B,
                        (const float*)(t->G + (int64_t)(T - 1) * B * G4), (const float*)(t->Cs + (int64_t)T * B * U),
                        (const float*)(t->Cs + (int64_t)(T - 1) * B * U), t->dc, dZl + (int64_t)(T - 1) * B * G4, B);
     RDL_CK(hipGetLastError(), "rdl cell_bwd_kernel");
+    if (bf16_cell(t)) {   // [dP_s | dh_{s-1}] from the transposed bf16 image, cell backward of step s - 1 fused
+        const unsigned gx = (unsigned)((B + BF_ROWS - 1) / BF_ROWS);
+        for (int s = T - 1; s >= 0; --s) {
+            BfDgradArgs a{};
+            a.dz = dZl + (int64_t)s * B * G4;
+            a.WB = t->wimg + BF_WF_GROUPS;
+            a.dP = t->dP + (int64_t)s * B * 32;
+            a.B = B;
+            a.cb0 = 0;
+            a.cb1 = 2;   // step 0: its dP alone
+            if (s > 0) {
+                a.cb1 = BF_NCB;
+                a.dHh = t->dHh + (int64_t)(s - 1) * B * U;
+                a.G = t->G + (int64_t)(s - 1) * B * G4;
+                a.ct = t->Cs + (int64_t)s * B * U;
+                a.cp = t->Cs + (int64_t)(s - 1) * B * U;
+                a.dc = t->dc;
+                a.dzo = dZl + (int64_t)(s - 1) * B * G4;
+            }
+            hipLaunchKernelGGL(lstm_bf16_dgrad_kernel, dim3(gx), dim3(256), 0, t->stream, a);
+            RDL_CK(hipGetLastError(), "rdl lstm_bf16_dgrad_kernel");
+        }
+    } else
     for (int s = T - 1; s > 0; --s) {
         rdg::GemmArgs g{};
         g.M = (int)B; g.N = U; g.K = G4;
@@ -1764,7 +1820,15 @@ int run_backward(rdl_trainer* t, const float* prev, const float* tgt, int64_t B,
     }
     // LSTM weights: dWl = [x | h_prev]^T dz over all rows (in the persistent BPTT for small
     // batches); dbl; then dp -> dWp, dbp
-    if (!persistent(t, B))
+    if (bf16_cell(t)) {   // split-K over the rows, the partials summed in split order
+        const int ns = bf_wg_splits(R);
+        hipLaunchKernelGGL(lstm_bf16_wgrad_kernel, dim3((G4 + 63) / 64, (unsigned)ns), dim3(256), 0, t->stream,
+                           (const float*)t->X, (const float*)t->H, (const float*)dZl, t->wpart, R, bf_wg_chunk(R));
+        RDL_CK(hipGetLastError(), "rdl lstm_bf16_wgrad_kernel");
+        hipLaunchKernelGGL(lstm_bf16_wgrad_reduce_kernel, dim3((BF_KWL * G4 + 255) / 256), dim3(256), 0, t->stream,
+                           (const float*)t->wpart, ns, g + OFF_WL);
+        RDL_CK(hipGetLastError(), "rdl lstm_bf16_wgrad_reduce_kernel");
+    } else if (!persistent(t, B))
         RDL_CK(mm2(t, ga(XI, G4, Ri, t->X, XLD, 1, dZl, G4, 0, g + OFF_WL, G4),
                    ga(U, G4, Ri, t->H, U, 1, dZl, G4, 0, g + OFF_WL + XI * G4, G4)),
                "rdl dWl x | h");
@@ -1779,7 +1843,8 @@ int run_backward(rdl_trainer* t, const float* prev, const float* tgt, int64_t B,
         hipLaunchKernelGGL(dense32_grad_kernel, dim3(160), dim3(256), 0, t->stream, P, (const float*)t->qbuf, g);
         RDL_CK(hipGetLastError(), "rdl dense32_grad_kernel");
     } else {
-        RDL_CK(mm(t, Ri, 32, G4, dZl, G4, 0, P + OFF_WL + 11 * G4, G4, 1, t->dP, 32), "rdl dP");
+        if (!bf16_cell(t))   // (bf16: the data gradient launches wrote dP)
+            RDL_CK(mm(t, Ri, 32, G4, dZl, G4, 0, P + OFF_WL + 11 * G4, G4, 1, t->dP, 32), "rdl dP");
         RDL_CK(mm(t, 4, 32, Ri, prev, 4, 1, t->dP, 32, 0, g + OFF_WP, 32), "rdl dWp");
         RDL_CK(colsum(t, t->dP, R, 32, 32, g + OFF_BP), "rdl dbp");
     }
@@ -1790,7 +1855,7 @@ int launch_adam(rdl_trainer* t) {
     AdamArgs a{t->grad, t->params, t->wpack, t->m, t->v, t->ctl, t->cfg.lr, t->cfg.beta1, t->cfg.beta2, t->cfg.eps, t->np};
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t->np + 255) / 256)), dim3(256), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "rdl adam_kernel");
-    return RD_OK;
+    return bf16_cell(t) ? bf16_images(t) : RD_OK;
 }
 
 bool bad_windows(const rdl_trainer* t, int64_t B) { return B <= 0 || B > t->Bmax; }
@@ -1901,7 +1966,13 @@ extern "C" {
 int64_t rdl_param_count(int32_t steps) { return steps > 0 ? params_of(steps) : -1; }
 
 int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_stream) {
+    return rdl_create_dtype(out, cfg, RDL_DTYPE_F32, device, hip_stream);
+}
+
+int rdl_create_dtype(rdl_trainer** out, const rdl_config* cfg, int32_t dtype, int device, void* hip_stream) {
     if (!out || !cfg) return rd::set_error(RD_EINVAL, "rdl_create: null argument");
+    if (dtype != RDL_DTYPE_F32 && dtype != RDL_DTYPE_BF16)
+        return rd::set_error(RD_EINVAL, "rdl_create_dtype: unknown dtype %d", (int)dtype);
     if ((cfg->loss != RDL_LOSS_MSE && cfg->loss != RDL_LOSS_KL) || !(cfg->lr > 0) || cfg->steps <= 0 ||
         cfg->max_windows <= 0 || (int64_t)cfg->steps * cfg->max_windows > ((int64_t)1 << 22) || cfg->metrics_len < 0 ||
         !(cfg->keep_prob > 0.0f && cfg->keep_prob <= 1.0f) || cfg->row_base < 0 ||
@@ -1917,6 +1988,7 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
     t->cus = rd::cu_count(device);
     t->stream = (hipStream_t)hip_stream;
     t->T = cfg->steps;
+    t->dtype = dtype;
     t->np = params_of(t->T);
     t->Bmax = cfg->max_windows;
     const int64_t R = (int64_t)t->T * t->Bmax, B = t->Bmax;
@@ -1967,6 +2039,10 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
     alloc(&t->qbuf, 4 * G4);
     alloc(&t->tnet, tch::P_TOT + 2 * tch::OBD);
     alloc(&t->eimg, EV_IMG);
+    if (bf16_cell(t)) {
+        if (e == hipSuccess) e = hipMalloc((void**)&t->wimg, sizeof(bf16x8) * BF_IMG_GROUPS);
+        alloc(&t->wpart, std::min<int64_t>(BF_WG_SPLITS, (R + BF_WG_CHUNK - 1) / BF_WG_CHUNK) * BF_KWL * G4);
+    }
     if (e == hipSuccess) e = hipMemsetAsync(t->bar, 0, sizeof(uint32_t) * 4, t->stream);
     t->grad = t->own_grad;
     if (e != hipSuccess) {
@@ -1988,6 +2064,11 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
         rdl_destroy(t);
         return rc;
     }
+    if (bf16_cell(t))   // the images of the zero master
+        if (int rc = bf16_images(t)) {
+            rdl_destroy(t);
+            return rc;
+        }
     *out = t;
     return RD_OK;
 }
@@ -1997,11 +2078,13 @@ int rdl_destroy(rdl_trainer* t) {
     rd::DeviceGuard dg(t->device);
     float* bufs[] = {t->params, t->m, t->v, t->own_grad, t->X, t->H, t->Cs, t->Z, t->G, t->A1, t->A2, t->A3, t->A4,
                      t->Y, t->dY, t->D32, t->D64a, t->D128, t->D64b, t->dHh, t->dP, t->dhn, t->dc, t->split,
-                     t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack, t->tnet, t->eimg};
+                     t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack, t->tnet, t->eimg,
+                     t->wpart};
     for (float* p : bufs)
         if (p) (void)hipFree(p);
     free_envs(t);
     if (t->hx) (void)hipFree(t->hx);
+    if (t->wimg) (void)hipFree(t->wimg);
     if (t->ctl) (void)hipFree(t->ctl);
     if (t->bar) (void)hipFree(t->bar);
     delete t;
@@ -2023,7 +2106,7 @@ int rdl_set_params(rdl_trainer* t, const float* params) {
     hipLaunchKernelGGL(pack_heads_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream,
                        (const float*)t->params, t->wpack, t->T);
     RD_HIP(hipGetLastError(), "rdl_set_params: pack_heads_kernel");
-    return RD_OK;
+    return bf16_cell(t) ? bf16_images(t) : RD_OK;
 }
 
 int rdl_get_params(rdl_trainer* t, float* params) {

@@ -47,8 +47,9 @@ def _restore(st, restore: bool, path: str | None, log):
 def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EPISODES, loss: str = "kl",
           lr: float = 1e-3, keep_prob: float = 1.0, seed: int = 0, device="cuda:0", teacher_path: str | None = None,
           warmup_episodes: int = 2 * LSTM_BATCH_SIZE, student_path: str | None = None, log=print,
-          gym_env: bool = False, store_dir: str | None = None, pool: str = "reference"):
-    """Returns (student trainer, dataset, per-episode summed training loss).  ``store_dir``:
+          gym_env: bool = False, store_dir: str | None = None, pool: str = "reference", dtype: str = "f32"):
+    """Returns (student trainer, dataset, per-episode summed training loss).  ``dtype``:
+    StudentLstmConfig.dtype ("bf16": the cell matrix's products on the bf16 MFMAs).  ``store_dir``:
     the dataset's page directory (lstm_train.py:104-109); episodes are dumped to it every
     MAX_CAPACITY episodes (:200) and its stored pages join the training pool (dataset.py:
     164-177); ``pool="ring"`` draws windows uniformly from the device ring instead.  With
@@ -60,7 +61,8 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
     teacher = TeacherAgent(restore=teacher_path is not None, path=teacher_path)   # always restored (ref. :29)
     tq = DistillTrainer(DistillConfig(n_envs=64, seed=seed), device=device, teacher=teacher.pi)
     st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed,
-                                              steps=STEPS_UNROLLED, max_windows=LSTM_BATCH_SIZE), device=device)
+                                              steps=STEPS_UNROLLED, max_windows=LSTM_BATCH_SIZE, dtype=dtype),
+                            device=device)
     dataset = DeviceDataset(device=device, seed=seed, batch_size=LSTM_BATCH_SIZE, steps_unrolled=STEPS_UNROLLED,
                             store=PageStore(store_dir) if store_dir else None, pool=pool)
     _restore(st, restore, student_path, log)
@@ -114,7 +116,7 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
 # -- the LSTM student distilled on-policy over many envs ---------------------------------------
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-3,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
-               eval_every: int = 0, eval_envs: int = 4096):
+               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32"):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -127,6 +129,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     the trainer is created with ``max_windows`` = B.  Its activations are about 2,900 floats per
     window position, 116 KB per window at T = 10: 4.8 MB per env, 1.2 GB at 256 envs, 19 GB at 4,096;
     T x B is at most 2^22 (n_envs <= 10,229 at the defaults).  A few hundred envs is the modest choice.
+    ``dtype``: StudentLstmConfig.dtype; with "bf16" the training pass runs the cell matrix's products
+    on the bf16 MFMAs while the envs are still stepped with the f32 master weights.
     ``teacher``: an MlpPolicyParams (default: the synthetic teacher DistillTrainer defaults to).
     Returns (trainer, history), history rows (optimiser step, loss, action-MSE, mean step reward) with
     the loss of the trainer's metrics ring (the sum over the batch's T x B rows for "kl"), the
@@ -141,7 +145,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     if n < 1 or K < 50 or K % 50:
         raise ValueError("n_envs >= 1 and accum_steps a positive multiple of 50")
     st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, steps=T,
-                                              max_windows=n * (K // 50) * (51 - T), metrics_len=steps), device=device)
+                                              max_windows=n * (K // 50) * (51 - T), metrics_len=steps,
+                                              dtype=dtype), device=device)
     st.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     st.attach_envs(n, seed=seed, accum_steps=K)
     rew = torch.zeros(steps, device=st.device)
@@ -160,7 +165,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
 def train_bptt(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EPISODES, loss: str = "kl",
                lr: float = 1e-3, keep_prob: float = 1.0, seed: int = 0, device="cuda:0", teacher_path: str | None = None,
                warmup_episodes: int = 2 * LSTM_BATCH_SIZE, student_path: str | None = None, log=print,
-               gym_env: bool = False, store_dir: str | None = None, pool: str = "reference"):
+               gym_env: bool = False, store_dir: str | None = None, pool: str = "reference", dtype: str = "f32"):
     """The truncated-BPTT variant of the driver (reference backup/lstm_bbpt.py:18-208), same
     graph, loss and Adam.  After the teacher warm-up (:115-139) each round is
       * one BPTT pass (:141-158): ``dataset.bptt_batches()`` -- LSTM_BATCH_SIZE episodes, the
@@ -175,7 +180,8 @@ def train_bptt(train: bool = True, restore: bool = False, *, episodes: int = TOT
     teacher = TeacherAgent(restore=teacher_path is not None, path=teacher_path)   # always restored (ref. :29)
     tq = DistillTrainer(DistillConfig(n_envs=64, seed=seed), device=device, teacher=teacher.pi)
     st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed,
-                                              steps=STEPS_UNROLLED, max_windows=LSTM_BATCH_SIZE), device=device)
+                                              steps=STEPS_UNROLLED, max_windows=LSTM_BATCH_SIZE, dtype=dtype),
+                            device=device)
     dataset = DeviceDataset(device=device, seed=seed, batch_size=LSTM_BATCH_SIZE, steps_unrolled=STEPS_UNROLLED,
                             store=PageStore(store_dir) if store_dir else None, pool=pool)
     _restore(st, restore, student_path, log)

@@ -6,6 +6,11 @@ LSTMCell(200), a 200-64-128-64-32-4 head per unrolled step), ``kl_loss`` (loss.p
 csrc/student_lstm.hip.  Tensors are the reference's window layout: ob [T, B, 11],
 prev_pdflat [T, B, 4], t_pdflat / pdflat [T, B, 4], state [2, B, 200] = (c, m).
 
+``StudentLstmConfig(dtype="bf16")`` (rdl_create_dtype) runs the three products of the cell matrix on
+the bf16 MFMAs in forward / rollout / step and the training pass of rollout_envs / step_envs, with
+f32 master weights, heads and sums; evaluate and act_envs stay f32 on the master weights, and the
+checkpoint is the f32 master plus slots either way.
+
 Multi-GPU: windows sharded contiguously (row_base = first global window), one
 all_reduce(SUM) of the flat gradient (511,880 floats at T = 10: the shared cell and one
 head per unrolled step) per optimiser step.
@@ -48,6 +53,7 @@ def n_params(T: int = STEPS_UNROLLED) -> int:
 
 N_PARAMS = n_params(STEPS_UNROLLED)   # 511,880 at the reference's T = 10
 LOSSES = {"mse": 0, "kl": 1}
+DTYPES = {"f32": 0, "bf16": 1}            # RDL_DTYPE_*
 
 
 class RdlConfig(ctypes.Structure):
@@ -80,6 +86,7 @@ nat.register({
     "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
     "rdl_param_count": (I64, [I32]),
     "rdl_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdlConfig), INT, P]),
+    "rdl_create_dtype": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdlConfig), I32, INT, P]),
     "rdl_destroy": (INT, [P]),
     "rdl_set_stream": (INT, [P, P]),
     "rdl_set_params": (INT, [P, P]),
@@ -141,6 +148,19 @@ class StudentLstmConfig:
     metrics_len: int = 4096
     step_recurrence: bool = False     # force the per-step recurrence launches (else: persistent at <= 32 windows)
     layer_head: bool = False          # force the per-layer head GEMMs (else: one launch at <= 16,384 rows)
+    dtype: str = "f32"                # "bf16": the cell matrix's three products (forward, data and weight
+                                      # gradient) on the bf16 MFMAs in forward / rollout / step and the training
+                                      # pass of the envs calls; f32 master, sums, heads; evaluate / act_envs stay
+                                      # f32; always the per-step recurrence (step_recurrence has no effect)
+
+    def __post_init__(self):
+        self.native_dtype()
+
+    def native_dtype(self) -> int:
+        """RDL_DTYPE_* of ``dtype``: what rdl_create_dtype takes."""
+        if not isinstance(self.dtype, str) or self.dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(DTYPES)}, got {self.dtype!r}")
+        return DTYPES[self.dtype]
 
 
 class StudentLstmTrainer:
@@ -152,6 +172,7 @@ class StudentLstmTrainer:
             raise ValueError("StudentLstmTrainer runs on a GPU (HIP) device only; there is no CPU path")
         self.rank, self.world, self.pg = rank, world_size, process_group
         self.T = int(self.cfg.steps)
+        dtype = self.cfg.native_dtype()   # a bad dtype raises before any native call
         self._lib = nat.load()
         self.n_params = n_params(self.T)
         assert self._lib.rdl_param_count(self.T) == self.n_params
@@ -162,8 +183,8 @@ class StudentLstmTrainer:
                       kernels=int(bool(self.cfg.step_recurrence)) | 2 * int(bool(self.cfg.layer_head)))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(self._lib.rdl_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
-                                           nat.stream_handle(self.device)), "rdl_create")
+            nat.check(self._lib.rdl_create_dtype(ctypes.byref(h), ctypes.byref(c), dtype, self.device.index or 0,
+                                                 nat.stream_handle(self.device)), "rdl_create_dtype")
         self._h = h
         self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._envs = None     # attach_envs()'s buffers
