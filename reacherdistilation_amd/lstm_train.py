@@ -116,7 +116,8 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
 # -- the LSTM student distilled on-policy over many envs ---------------------------------------
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-3,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
-               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32"):
+               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
+               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -137,23 +138,49 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     action-MSE the mean over rows and both action dims against the teacher, the reward the mean over
     the call's env steps.  With ``eval_every`` > 0 returns (trainer, history, evals): evals rows
     (optimiser step, mean return of StudentLstmTrainer.evaluate over ``eval_envs`` fresh envs, one
-    episode) after every eval_every-th step.  Single GPU."""
+    episode) after every eval_every-th step.  Single GPU.
+    ``replay_capacity`` > 0 trains from a replay.ReplayRing of that many episodes instead (the aggregate
+    of the reference's DAgger loop, dataset.py:166-194): each iteration is act_envs (``accum_steps`` env
+    steps, no training), ring.push_steps of its (accum_steps / 50) n_envs episodes, then
+    ``updates_per_act`` x { ring.sample_windows(T, ``replay_windows``, recent=``replay_recent``), step }:
+    the batch no longer follows from the env count (``max_windows`` = replay_windows), and its windows
+    come from old and new episodes alike, drawn on the device.  History rows stay per optimiser step
+    (the reward that of the act call the step followed); an act call is stepped with the teacher while
+    the optimiser step it precedes is a warm-up step."""
     from .policy import synthetic_teacher
     n, steps, K, T = int(n_envs), int(opt_steps), int(accum_steps), STEPS_UNROLLED
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
         raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
     if n < 1 or K < 50 or K % 50:
         raise ValueError("n_envs >= 1 and accum_steps a positive multiple of 50")
+    cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
+    if cap < 0 or (cap and (Bw < 1 or upa < 1 or int(replay_recent) < 0 or n * (K // 50) > cap)):
+        raise ValueError("replay_capacity >= (accum_steps / 50) n_envs, replay_windows >= 1, updates_per_act >= 1 "
+                         "and replay_recent >= 0")
     st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, steps=T,
-                                              max_windows=n * (K // 50) * (51 - T), metrics_len=steps,
-                                              dtype=dtype), device=device)
+                                              max_windows=Bw if cap else n * (K // 50) * (51 - T),
+                                              metrics_len=steps, dtype=dtype), device=device)
     st.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     st.attach_envs(n, seed=seed, accum_steps=K)
     rew = torch.zeros(steps, device=st.device)
     evals = []
+    ring = None
+    if cap:
+        from .replay import ReplayRing
+        ring = st.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
     for k in range(steps):
-        r = st.step_envs("teacher" if k < int(warmup_steps) else "student")
-        rew[k] = r.reward.mean()
+        act_with = "teacher" if k < int(warmup_steps) else "student"
+        if ring is None:
+            r = st.step_envs(act_with)
+            rew[k] = r.reward.mean()
+        else:
+            if k % upa == 0:
+                r = st.act_envs(act_with)
+                ring.push_steps(r.records)
+                mean_reward = r.reward.mean()
+            ob_w, prev_w, t_w, _ = ring.sample_windows(T, Bw, recent=int(replay_recent))
+            st.step(ob_w, prev_w, t_w)
+            rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:
             evals.append((k + 1, float(st.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
     m = st.metrics(steps)

@@ -119,7 +119,8 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
 # -- the reference student distilled on-policy over many envs ----------------------------------
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-4,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
-               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32"):
+               eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
+               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -135,20 +136,43 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     (optimiser step, mean return of StudentMlpTrainer.evaluate over ``eval_envs`` fresh envs, one
     episode) after every eval_every-th step -- the reference's average reward per keep_prob.
     ``dtype``: StudentMlpConfig.dtype ("bf16": mixed precision in the env, training and evaluation
-    launches alike)."""
+    launches alike).
+    ``replay_capacity`` > 0 trains from a replay.ReplayRing of that many episodes instead (the aggregate
+    of the reference's DAgger loop): each iteration is act_envs (``accum_steps`` env steps, a multiple of
+    50, no training), ring.push_rows of its (accum_steps / 50) n_envs episodes, then ``updates_per_act`` x
+    { ring.sample_rows(``replay_windows`` rows, recent=``replay_recent``), step }.  History rows stay per
+    optimiser step (the reward that of the act call the step followed); an act call is stepped with the
+    teacher while the optimiser step it precedes is a warm-up step."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
         raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
+    cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
+    if cap < 0 or (cap and (Bw < 1 or upa < 1 or int(replay_recent) < 0 or K < 50 or K % 50 or n * (K // 50) > cap)):
+        raise ValueError("with a replay ring: accum_steps a positive multiple of 50, replay_capacity >= "
+                         "(accum_steps / 50) n_envs, replay_windows >= 1, updates_per_act >= 1, replay_recent >= 0")
     sm = StudentMlpTrainer(StudentMlpConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, metrics_len=steps,
                                             dtype=dtype), device=device)
     sm.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     sm.attach_envs(n, seed=seed, accum_steps=K)
     rew = torch.zeros(steps, device=sm.device)
     evals = []
+    ring = None
+    if cap:
+        from .replay import ReplayRing
+        ring = sm.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
     for k in range(steps):
-        r = sm.step_envs("teacher" if k < int(warmup_steps) else "student")
-        rew[k] = r.reward.mean()
+        act_with = "teacher" if k < int(warmup_steps) else "student"
+        if ring is None:
+            r = sm.step_envs(act_with)
+            rew[k] = r.reward.mean()
+        else:
+            if k % upa == 0:
+                r = sm.act_envs(act_with)
+                ring.push_rows(r, stepped_with=float(act_with == "student"))
+                mean_reward = r.reward.mean()
+            sm.step(*ring.sample_rows(Bw, recent=int(replay_recent)))
+            rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:
             evals.append((k + 1, float(sm.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
     m = sm.metrics(steps)
