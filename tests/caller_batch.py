@@ -106,8 +106,20 @@ def _forward_error(p, ob):
 def single_row_error_bound(mode, seed, loss):
     """The worst-case first-order f32 error of the gradient of rows(1, seed), per entry, as a
     multiple of TOL_ENTRY x M_e (its largest entry)."""
+    return row_error_bound(mode, *rows(1, seed), loss)
+
+
+def row_error_bound(mode, ob, t, loss):
+    """single_row_error_bound() of a given row: observation ob [1, 11] and, in rows mode, its
+    recorded pdflat t [1, 4]."""
+    e, M = row_error_terms(mode, ob, t, loss)
+    return float((e[M > 0] / M[M > 0]).max() / parity.TOL_ENTRY)
+
+
+def row_error_terms(mode, ob, t, loss):
+    """(e, M) of row_error_bound(): the first-order error bound and the scale M_e per gradient
+    entry, both at n_global = 1 (rows of one launch add in each)."""
     teacher, student = nets()
-    ob, t = rows(1, seed)
     q, f, e_h1, e_h2, e_ms = _forward_error(student, ob)
     z, h1, h2 = f["z"][0], f["h1"][0], f["h2"][0]
     if mode == "obs":
@@ -133,8 +145,7 @@ def single_row_error_bound(mode, seed, loss):
     e_dz1 = (PRODUCT_ERR * (W2 @ np.abs(dz2)) + W2 @ e_dz2) * s1 + np.abs(dh1) * 2 * np.abs(h1) * e_h1
     e_W1 = np.outer(np.abs(z), e_dz1 + 2 * ULP * np.abs(dh1 * s1))
     e = pn.pack(e_W1, e_dz1, e_W2, e_dz2, e_W3, e_dm, e_ls)
-    M = oracle(mode, ob, t, loss, 1)[1]
-    return float((e[M > 0] / M[M > 0]).max() / parity.TOL_ENTRY)
+    return e, oracle(mode, ob, t, loss, 1)[1]
 
 
 def single_row_ok(seed):
@@ -200,3 +211,40 @@ def row_contributions(mode, ob, t, loss, n_global, sel):
     dls = (np.exp(2 * fs["logstd"]) / np.exp(2 * lt[sel]) - 1.0).sum(0) if loss == "kl" else np.zeros(2)
     f = {k: (v[sel] if getattr(v, "ndim", 0) == 2 else v) for k, v in fs.items()}
     return pn.backward(sp, f, dmean[sel], dls)
+
+
+# ---------------------------------------------------------------- the bf16 student as a kernel forms it
+# (f32 accumulation and the kernels' f32 tanh in place of the bf16 oracle's f64: the stand-in that
+# tells whether a batch leaves room for flipped bf16 roundings; tests/test_caller_batch_gpu.py,
+# tests/env_batch.py)
+def tanh_f32(pre):
+    """tanh as the kernels form it (rd_device.h tanh_pre), every step rounded to f32:
+    1 - 2 / (2^y + 1), y = 2 log2(e) pre."""
+    f32 = np.float32
+    y = (pre * f32(2.8853900817779268)).astype(f32)
+    e = np.exp2(y.astype(np.float64)).astype(f32)
+    r = (1.0 / (e + f32(1)).astype(f32).astype(np.float64)).astype(f32)
+    return (1.0 - 2.0 * r.astype(np.float64)).astype(f32).astype(np.float64)
+
+
+def forward_bf16_f32_accumulation(p, obmu, obsd, ob):
+    """pn.forward_bf16 with the two hidden layers' pre-activations accumulated in f32 (numpy's f32
+    matmul) and their tanh formed in f32, as a kernel does, instead of f64."""
+    q = pn.unpack(np.asarray(p, np.float64))
+    f32 = np.float32
+    rs = (f32(1) / np.asarray(obsd, f32)).astype(f32)
+    z = np.clip((np.asarray(ob, f32) - np.asarray(obmu, f32)) * rs, f32(-5), f32(5)).astype(f32)
+    zb = pn.bf16(z)
+    h1 = tanh_f32(zb.astype(f32) @ pn.bf16(q["W1"]).astype(f32) + q["b1"].astype(f32))
+    h2 = tanh_f32(pn.bf16(h1).astype(f32) @ pn.bf16(q["W2"]).astype(f32) + q["b2"].astype(f32))
+    return dict(z=z.astype(np.float64), zb=zb, h1=h1, h2=h2, mean=h2 @ pn.bf16(q["W3"]) + q["b3"], logstd=q["ls"])
+
+
+def teacher_mean_f32(p, ob):
+    """The f32 teacher's mean with every layer formed in f32."""
+    f32 = np.float32
+    q = {k: v.astype(f32) for k, v in pn.unpack(p.flat).items()}
+    z = np.clip((np.asarray(ob, f32) - p.ob_mean) * (f32(1) / p.ob_std).astype(f32), f32(-5), f32(5)).astype(f32)
+    h1 = tanh_f32(z @ q["W1"] + q["b1"]).astype(f32)
+    h2 = tanh_f32(h1 @ q["W2"] + q["b2"]).astype(f32)
+    return (h2 @ q["W3"] + q["b3"]).astype(f32)

@@ -49,6 +49,7 @@ CASES = [
     (20000, 6, "mse", "student", True, "f32"),     # ragged, DAgger, 16-env groups, 2 groups on some pairs
     (4096, 3, "kl", "teacher", True, "f32"),       # config 2's size (plain layout, not the helper pairs)
     (131072, 3, "mse", "student", True, "bf16"),   # config 5's shard: bf16 student, DAgger
+    (131072, 3, "mse", "student", False, "bf16"),  # ... with the exact-f32 teacher (the fourth K-step instance)
 ]
 
 

@@ -116,37 +116,8 @@ BF16_SEEDS = {203: 203, 499: 500, 1000: 1000}
 BF16_NS = sorted(BF16_SEEDS)
 
 
-def _tanh_f32(pre):
-    """tanh as the kernels form it (rd_device.h tanh_pre), every step rounded to f32:
-    1 - 2 / (2^y + 1), y = 2 log2(e) pre."""
-    f32 = np.float32
-    y = (pre * f32(2.8853900817779268)).astype(f32)
-    e = np.exp2(y.astype(np.float64)).astype(f32)
-    r = (1.0 / (e + f32(1)).astype(f32).astype(np.float64)).astype(f32)
-    return (1.0 - 2.0 * r.astype(np.float64)).astype(f32).astype(np.float64)
-
-
-def _forward_bf16_f32_accumulation(p, obmu, obsd, ob):
-    """pn.forward_bf16 with the two hidden layers' pre-activations accumulated in f32 (numpy's f32
-    matmul) and their tanh formed in f32, as a kernel does, instead of f64."""
-    q = pn.unpack(np.asarray(p, np.float64))
-    f32 = np.float32
-    rs = (f32(1) / np.asarray(obsd, f32)).astype(f32)
-    z = np.clip((np.asarray(ob, f32) - np.asarray(obmu, f32)) * rs, f32(-5), f32(5)).astype(f32)
-    zb = pn.bf16(z)
-    h1 = _tanh_f32(zb.astype(f32) @ pn.bf16(q["W1"]).astype(f32) + q["b1"].astype(f32))
-    h2 = _tanh_f32(pn.bf16(h1).astype(f32) @ pn.bf16(q["W2"]).astype(f32) + q["b2"].astype(f32))
-    return dict(z=z.astype(np.float64), zb=zb, h1=h1, h2=h2, mean=h2 @ pn.bf16(q["W3"]) + q["b3"], logstd=q["ls"])
-
-
-def _teacher_mean_f32(p, ob):
-    """The f32 teacher's mean with every layer formed in f32."""
-    f32 = np.float32
-    q = {k: v.astype(f32) for k, v in pn.unpack(p.flat).items()}
-    z = np.clip((np.asarray(ob, f32) - p.ob_mean) * (f32(1) / p.ob_std).astype(f32), f32(-5), f32(5)).astype(f32)
-    h1 = _tanh_f32(z @ q["W1"] + q["b1"]).astype(f32)
-    h2 = _tanh_f32(h1 @ q["W2"] + q["b2"]).astype(f32)
-    return (h2 @ q["W3"] + q["b3"]).astype(f32)
+_tanh_f32, _forward_bf16_f32_accumulation, _teacher_mean_f32 = (cb.tanh_f32, cb.forward_bf16_f32_accumulation,
+                                                                cb.teacher_mean_f32)
 
 
 def _bf16_accumulation_ratios(mode, n, loss, seed):
