@@ -57,7 +57,7 @@ struct GemmArgs {
 };
 
 // TF1 LSTMCell backward at one (row, unit) with dh = dh_head + dh_next: the arithmetic of
-// the standalone cell kernel in csrc/student_lstm.hip, operation for operation (bitwise).
+// the standalone cell kernel (cell_bwd_kernel, csrc/student_lstm_optim.h), operation for operation (bitwise).
 __device__ __forceinline__ void lstm_bwd_point(const GemmArgs& g, int64_t row, int u, float dh_next) {
     const int U = g.N;
     const int64_t idx = row * U + u;

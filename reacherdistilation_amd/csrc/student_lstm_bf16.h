@@ -5,7 +5,7 @@
 // cell backward of the step before in the epilogue) and the dWl GEMMs (weight gradient, split-K).
 // Master weights, biases, the prev_pdflat projection, the cell's point-wise arithmetic, the heads,
 // the loss, dbl, dWp, dbp and every sum stay f32.  Included inside student_lstm.hip's anonymous
-// namespace: U, G4, XI, XLD, OFF_WL and sigm are its.
+// namespace: U, G4, XI, XLD, OFF_WL and sigm are student_lstm_layout.h's.
 //
 // Operands.  Activations stay f32 in HBM in the f32 path's buffers and are rounded where they
 // are loaded (v_cvt_pk_bf16_f32, round-to-nearest-even); the weights come from two bf16 images of

@@ -1,7 +1,7 @@
 // One closed-loop step of the LSTM student on a block of 16 envs: what student_lstm_evaluate_kernel
 // (student_lstm_eval.h) and student_lstm_envs_kernel (student_lstm_envs.h) both run, once.  Included
-// inside student_lstm.hip's anonymous namespace after head_layer; expects rd_device.h, rd_gemm.h,
-// rd_physics.h and the file's constants.
+// inside student_lstm.hip's anonymous namespace after student_lstm_head.h (head_layer); expects
+// rd_device.h, rd_gemm.h, rd_physics.h and student_lstm_layout.h's constants.
 //
 // A workgroup (8 waves, two per SIMD) owns a block of 16 envs -- one MFMA row tile:
 //  * lanes 0..15 of wave 0 keep the envs (rd::observe<true>, rd::env_step<true>: rd_step's functions);

@@ -1,7 +1,9 @@
 """A/B of two builds on the same steps: writes the student parameters and the last gradient
 after a few fused steps of several configs to an .npz (the build is chosen with RD_LIB), so
 two runs can be compared bit for bit.
-usage: RD_LIB=libreacher_x.so python scripts/bitwise_ab.py out.npz  (GPU)
+--lstm runs the LSTM student's case set instead: three rdl_step calls per case and loss from seeded
+parameters and windows; parameters, gradient, the three metrics rows and the final state are written.
+usage: RD_LIB=libreacher_x.so python scripts/bitwise_ab.py [--lstm] out.npz  (GPU)
        python scripts/bitwise_ab.py --compare a.npz b.npz"""
 import os
 import sys
@@ -44,6 +46,48 @@ def run(out):
     print("wrote", out, flush=True)
 
 
+LSTM_CASES = {   # name: (T, B, StudentLstmConfig overrides, with state0): every launch sequence of student_lstm.hip
+    "persist_20": (10, 20, {}, False),             # persistent cell, wide fused head with the loss, grad_finish_kernel
+    "step_20": (10, 20, dict(step_recurrence=True), False),   # per-step f32 cell, fused head, one loss block
+    "layers_20": (10, 20, dict(layer_head=True), False),      # persistent cell, per-layer head, dense32_grad_kernel
+    "step_t3_130": (3, 130, {}, False),            # per-step cell (B > 32), two loss blocks + metrics_kernel, GEMM tail
+    "head_narrow_1000": (10, 1000, {}, False),     # fused head, one tile per workgroup, four waves
+    "head_tiles_4100": (10, 4100, {}, False),      # fused head, several tiles per workgroup, two-level column sums
+    "bf16_20": (10, 20, dict(dtype="bf16"), False),           # bf16 cell, one weight-gradient split
+    "bf16_t3_130": (3, 130, dict(dtype="bf16"), False),       # bf16 cell, several splits
+    "state0_20": (10, 20, {}, True),
+    "state0_step_20": (10, 20, dict(step_recurrence=True), True),
+}
+
+
+def run_lstm(out):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from reacherdistilation_amd.student_lstm import StudentLstmConfig, StudentLstmTrainer
+    res = {}
+    for name, (T, B, kw, with_state) in LSTM_CASES.items():
+        rng = np.random.RandomState(11)
+        ob = rng.standard_normal((T, B, 11)).astype(np.float32)
+        prev = (0.5 * rng.standard_normal((T, B, 4))).astype(np.float32)
+        tgt = rng.uniform(-1.0, 0.5, (T, B, 4)).astype(np.float32)
+        st = (0.3 * rng.standard_normal((2, B, 200))).astype(np.float32) if with_state else None
+        for loss in ("mse", "kl"):
+            tr = StudentLstmTrainer(StudentLstmConfig(loss=loss, steps=T, max_windows=B, keep_prob=0.5, seed=5, **kw),
+                                    device="cuda:0")
+            for _ in range(3):
+                tr.step(ob, prev, tgt, st)
+            torch.cuda.synchronize()
+            key = f"{name}_{loss}"
+            res[key + "_params"] = tr.params().cpu().numpy()
+            res[key + "_grad"] = tr.grad().cpu().numpy()
+            res[key + "_metrics"] = tr.metrics(3)
+            res[key + "_state"] = tr.final_state(B).cpu().numpy()
+            tr.close()
+            print("ran", key, flush=True)
+    np.savez(out, **res)
+    print("wrote", out, flush=True)
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = 0
@@ -59,4 +103,7 @@ def compare(a, b):
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         sys.exit(1 if compare(sys.argv[2], sys.argv[3]) else 0)
-    run(sys.argv[1])
+    if sys.argv[1] == "--lstm":
+        run_lstm(sys.argv[2])
+    else:
+        run(sys.argv[1])
