@@ -43,10 +43,19 @@
  * path: the persistent kernels (at most 32 windows, latency bound) are f32 only and never launched
  * by it, so RDL_KERNELS_STEP_RECURRENCE has no effect on it; RDL_KERNELS_LAYER_HEAD and
  * rdl_head_path work as on an f32 handle (the head is f32 on either path).
- * Which calls stay f32, on the master weights: the one-record-per-env query -- rdl_evaluate,
- * rdl_envs_act and the act phase of rdl_rollout_envs / rdl_step_envs.  On a bf16 handle these are
- * bitwise what an f32 handle with the same parameters returns (evaluate measures the checkpointed
- * policy), and rdl_step_envs equals rdl_envs_act, then rdl_step (bf16) on the windows written.
+ * The closed-loop query -- the one-record-per-env query of rdl_evaluate, rdl_envs_act and the act
+ * phase of rdl_rollout_envs / rdl_step_envs -- has its own setting, rdl_set_query_dtype:
+ *   RDL_DTYPE_F32 (the default of every handle): the query stays f32, on the master weights.  On a
+ *     bf16 handle these calls are then bitwise what an f32 handle with the same parameters returns
+ *     (evaluate measures the checkpointed f32 policy), while the training pass sees the rounded
+ *     operands: the student that acts is not quite the student that is trained.
+ *   RDL_DTYPE_BF16 (bf16 handles only): one query step is exactly one rdl_forward of the handle on
+ *     that env's window from its carried (c, h): x formed in f32, z = bl + sum_k bf([x | h]_k)
+ *     bf(Wl_kc) from the handle's forward image (no per-call pack of Wl), the f32 cell, the f32 head
+ *     T-1; teacher, physics and records unchanged.  rdl_evaluate and rdl_envs_act are then bitwise
+ *     the stepwise loop { rdd_forward (teacher), rdl_forward on the window, rd_step } run with that
+ *     bf16 handle, whatever the grid; evaluate measures the policy as deployed in bf16.
+ * Under either setting rdl_step_envs equals rdl_envs_act, then rdl_step on the windows written.
  *
  * Conventions as in reacher.h: device pointers, asynchronous on the handle's stream,
  * 0 = OK, RD_EINVAL, -(hipError_t).  Multi-GPU: windows sharded by the caller (row_base =
@@ -105,6 +114,14 @@ int rdl_create(rdl_trainer** out, const rdl_config* cfg, int device, void* hip_s
 #define RDL_DTYPE_F32 0
 #define RDL_DTYPE_BF16 1
 int rdl_create_dtype(rdl_trainer** out, const rdl_config* cfg, int32_t dtype, int device, void* hip_stream);
+/* arithmetic of the closed-loop query (rdl_evaluate, rdl_envs_act, the act phase of
+ * rdl_rollout_envs / rdl_step_envs): RDL_DTYPE_F32 (the default) or RDL_DTYPE_BF16
+ * ("Arithmetic" above).  Host-only: no device call, no allocation, no synchronisation; the next
+ * call takes it, a captured call keeps the kernel it was captured with.  RD_EINVAL (the setting
+ * unchanged) for a null handle, an unknown dtype, and RDL_DTYPE_BF16 on a handle that was not
+ * created with RDL_DTYPE_BF16: it keeps no bf16 image, and its training would not match the query */
+int rdl_set_query_dtype(rdl_trainer* t, int32_t dtype);
+int rdl_query_dtype(const rdl_trainer* t);      /* RDL_DTYPE_*; -1 for NULL */
 int rdl_destroy(rdl_trainer* t);
 int rdl_set_stream(rdl_trainer* t, void* hip_stream);
 /* initialisation / saver.restore (lstm_train.py:82-107): params [RDL_PARAMS_T(steps)] */
@@ -170,7 +187,8 @@ int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, c
  *   reward r_s = env.step(S_s[0..1])
  * Same arithmetic as the stepwise path: the outputs are bitwise those of rd_reset, then 50 x
  * { rdd_forward (teacher), rdl_forward on the windows, rd_step with the student's mean }, for every
- * grid.  T is at most RDL_EVAL_MAX_STEPS, the records of history the kernel keeps on chip per env.
+ * grid -- rdl_forward being an f32 handle's under the f32 query and this bf16 handle's under the bf16
+ * query (rdl_set_query_dtype, "Arithmetic" above).  T is at most RDL_EVAL_MAX_STEPS, the records of history the kernel keeps on chip per env.
  * Outputs (device, caller-owned; final_dist, records and state_out may be NULL):
  *   returns    [episodes][n_envs]  r_0 + ... + r_49, f32, summed in step order
  *   final_dist [episodes][n_envs]  |fingertip - target| after the episode's last step
@@ -181,7 +199,8 @@ int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, c
  * No side effects on the trainer: parameters, Adam state and counter, gradient, metrics, the
  * activations rdl_final_state reads, the persistent kernels' barrier words and granule generation.
  * Asynchronous on the handle's stream, no host sync, no allocation (the packed image of the cell's
- * weights is the handle's, rebuilt on the stream by every call): capturable.
+ * weights is the handle's, rebuilt on the stream by every call; the bf16 query reads the handle's
+ * bf16 image, no launch): capturable.
  * RD_EINVAL: NULL trainer, config or returns; n_envs < 1 (or > 2^31); episodes < 1; negative
  * env_base, first_episode or grid (all checked before any device call and before the handle is
  * read); no teacher set; rdl_config.steps > RDL_EVAL_MAX_STEPS. */

@@ -24,8 +24,10 @@
 // rdl_create_dtype's RDL_DTYPE_BF16 sends the three products of the cell matrix Wl (the gate product of
 // each step, input half included; dh / dP; dWl) to the bf16 MFMA kernels of student_lstm_bf16.h, always
 // on this per-step path; everything else, and an f32 handle, runs what is described above.
+// rdl_set_query_dtype's RDL_DTYPE_BF16 also sends the gate product of the closed-loop query (rdl_evaluate,
+// the envs calls) to those MFMAs (student_lstm_query_bf16.h); by default it stays f32 on the master.
 //
-// One translation unit: the device code is the nine student_lstm_*.h included below, in the order the
+// One translation unit: the device code is the ten student_lstm_*.h included below, in the order the
 // kernels stand in the object.  This file keeps rdl_trainer, the choice of launches for a batch
 // (Path), one function per cell path and head path, and the C ABI.
 #include <hip/hip_runtime.h>
@@ -58,12 +60,14 @@ namespace {
 // one closed-loop step of a 16-env block, shared by the two below: tch::, the EV_* tiling,
 // lstm_eval_pack_kernel, the block's LDS and the ls_* pieces
 #include "student_lstm_query.h"
+// the bf16 mixed-precision cell (rdl_create_dtype's RDL_DTYPE_BF16): the Wl images and the three MFMA kernels
+#include "student_lstm_bf16.h"
+// the step's window positions on the bf16 cell (rdl_set_query_dtype): ls_positions_bf16, ls_positions_of
+#include "student_lstm_query_bf16.h"
 // the whole-episode evaluation (rdl_evaluate): student_lstm_evaluate_kernel
 #include "student_lstm_eval.h"
 // the persistent envs (rdl_envs_*, rdl_rollout_envs, rdl_step_envs): LsEnvsArgs, student_lstm_envs_kernel
 #include "student_lstm_envs.h"
-// the bf16 mixed-precision cell (rdl_create_dtype's RDL_DTYPE_BF16): the Wl images and the three MFMA kernels
-#include "student_lstm_bf16.h"
 
 }  // namespace
 
@@ -106,6 +110,8 @@ struct rdl_trainer {
     int dtype = RDL_DTYPE_F32;
     bf16x8* wimg = nullptr;
     float* wpart = nullptr;
+    // the closed-loop query's arithmetic (rdl_set_query_dtype): RDL_DTYPE_BF16 reads wimg's forward image
+    int qdtype = RDL_DTYPE_F32;
 };
 
 namespace {
@@ -167,6 +173,7 @@ int head_nb(int T, int64_t B) {
 bool head_wide(int T, int64_t B) { return (int64_t)T * ((B + HF_ROWS - 1) / HF_ROWS) <= HB_WIDE_GRID; }
 
 bool bf16_cell(const rdl_trainer* t) { return t->dtype == RDL_DTYPE_BF16; }
+bool bf16_query(const rdl_trainer* t) { return t->qdtype == RDL_DTYPE_BF16; }
 
 // The launches that a pass over B windows issues, decided once per call (path_of) and handed to
 // run_forward and run_backward: the persistent recurrence kernels for batches of at most PR_ROWS
@@ -534,8 +541,10 @@ int copy_final_state(rdl_trainer* t, int64_t B, float* state_out, const char* wh
     return RD_OK;
 }
 
-// the closed-loop kernels' packed image of Wl from the current parameters (student_lstm_query.h)
+// the closed-loop kernels' packed image of Wl from the current parameters (student_lstm_query.h);
+// the bf16 query reads the handle's forward image, which is current on the stream: no launch
 int launch_eval_pack(rdl_trainer* t) {
+    if (bf16_query(t)) return RD_OK;
     hipLaunchKernelGGL(lstm_eval_pack_kernel, dim3((EV_IMG + 255) / 256), dim3(256), 0, t->stream,
                        (const float*)t->params, t->eimg);
     RD_HIP(hipGetLastError(), "lstm_eval_pack_kernel launch");
@@ -557,7 +566,7 @@ LsEnvsArgs envs_args(const rdl_trainer* t) {
     a.seed = t->envs_seed;
     a.tnet = t->tnet;
     a.P = t->params;
-    a.img = t->eimg;
+    a.img = bf16_query(t) ? (const float*)t->wimg : t->eimg;
     a.state = t->env_state;
     a.aux = t->env_aux;
     a.clock = t->env_clock;
@@ -619,8 +628,9 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     a.steps = steps;
     const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = t->envs_grid > 0 ? t->envs_grid : t->cus;
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
-    if (stu) hipLaunchKernelGGL(student_lstm_envs_kernel<true>, grid, block, 0, t->stream, a);
-    else hipLaunchKernelGGL(student_lstm_envs_kernel<false>, grid, block, 0, t->stream, a);
+    auto* kern = !stu ? student_lstm_envs_kernel<false, false>
+                 : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
+    hipLaunchKernelGGL(kern, grid, block, 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_lstm_envs_kernel launch");
     return RD_OK;
 }
@@ -750,6 +760,19 @@ int rdl_create_dtype(rdl_trainer** out, const rdl_config* cfg, int32_t dtype, in
     *out = t;
     return RD_OK;
 }
+
+int rdl_set_query_dtype(rdl_trainer* t, int32_t dtype) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_set_query_dtype: null trainer");
+    if (dtype != RDL_DTYPE_F32 && dtype != RDL_DTYPE_BF16)
+        return rd::set_error(RD_EINVAL, "rdl_set_query_dtype: unknown dtype %d", (int)dtype);
+    if (dtype == RDL_DTYPE_BF16 && !bf16_cell(t))
+        return rd::set_error(RD_EINVAL, "rdl_set_query_dtype: dtype RDL_DTYPE_BF16 needs a handle created with "
+                                        "RDL_DTYPE_BF16 (rdl_create_dtype): an f32 handle keeps no bf16 image of Wl");
+    t->qdtype = dtype;
+    return RD_OK;
+}
+
+int rdl_query_dtype(const rdl_trainer* t) { return t ? t->qdtype : -1; }
 
 int rdl_destroy(rdl_trainer* t) {
     if (!t) return RD_OK;
@@ -946,7 +969,7 @@ int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0
     a.seed = cfg->seed;
     a.tnet = t->tnet;
     a.P = t->params;
-    a.img = t->eimg;
+    a.img = bf16_query(t) ? (const float*)t->wimg : t->eimg;
     a.draws = cfg->draws;
     a.state0 = state0;
     a.returns = returns;
@@ -958,8 +981,8 @@ int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0
     a.T = t->T;
     // a block of 16 envs per workgroup for the whole launch, one workgroup per CU (its LDS)
     const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = cfg->grid > 0 ? cfg->grid : t->cus;
-    hipLaunchKernelGGL(student_lstm_evaluate_kernel, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0,
-                       t->stream, a);
+    auto* kern = bf16_query(t) ? student_lstm_evaluate_kernel<true> : student_lstm_evaluate_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
     return RD_OK;
 }

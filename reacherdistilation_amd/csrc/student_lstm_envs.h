@@ -3,8 +3,8 @@
 // under the teacher's or the LSTM student's mean action, writes the K n records and the training
 // windows that lie wholly inside an episode, which the training path (rdl_rollout's launches) then
 // reads as any caller's windows (DESIGN.md §3 "On-policy distillation of the LSTM student").
-// Included inside student_lstm.hip's anonymous namespace after student_lstm_query.h, whose step it
-// runs: the workgroup's layout, the tiling and the pieces of a step are there.
+// Included inside student_lstm.hip's anonymous namespace after student_lstm_query.h and
+// student_lstm_query_bf16.h, whose step it runs: the workgroup's layout, the tiling and the pieces of a step are there.
 //
 // This kernel's own: the envs are kept between launches.  For its block of 16 envs a workgroup loads
 // from the handle's device arrays at entry, and writes back at exit,
@@ -42,7 +42,7 @@ struct LsEnvsArgs {
     uint64_t seed;
     const float* tnet;       // teacher net: params | ob mean | ob std
     const float* P;          // the student's flat parameters
-    const float* img;        // lstm_eval_pack_kernel's image of Wl [EV_IMG]
+    const float* img;        // lstm_eval_pack_kernel's image of Wl [EV_IMG]; BF16Q: the bf16 image WF
     float* state;            // [8][n] SoA (rd_get_state's layout)
     float* aux;              // [ENV_AUX][n]
     int32_t* clock;          // [2][n]: step of the episode, episode
@@ -63,7 +63,9 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
     if (i < a.n) rd::envs_reset_one<ENV_AUX>(a.state, a.aux, a.clock, a.n, i, a.seed, a.env_base);
 }
 
-template <bool STUDENT_ACTS>
+// BF16Q: the student's positions run on the bf16 cell (student_lstm_query_bf16.h; a.img is then the
+// handle's WF image)
+template <bool STUDENT_ACTS, bool BF16Q>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArgs a) {
     const LsThread q = ls_prologue<STUDENT_ACTS>(a.tnet, a.P, a.img, a.T);
     const int tid = q.tid, lane = q.lane, T = q.T;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArg
             if (STUDENT_ACTS) lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
             __syncthreads();
             ls_teacher(q, s);
-            if constexpr (STUDENT_ACTS) hp = ls_positions(q, s, hp);
+            if constexpr (STUDENT_ACTS) hp = ls_positions_of<BF16Q>(q, s, hp);
             else __syncthreads();   // T_s
             // the window of this query, if it lies inside the episode: records s-T+1 .. s from the ring
             // (T_s was published by the barriers above; the ring's next write follows the barriers below)
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArg
                 }
                 wrow += n;
             }
-            if constexpr (STUDENT_ACTS) ls_head(q, hp);
+            if constexpr (STUDENT_ACTS) ls_head<BF16Q>(q, hp);
             if (phys) {
                 float sp[4];
                 ls_record_tail<STUDENT_ACTS>(lane, s, rec, tp, sp);

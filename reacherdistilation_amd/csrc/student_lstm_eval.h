@@ -2,7 +2,7 @@
 // rollout launch rolls n evaluation envs through E consecutive 50-step episodes under the LSTM
 // student's mean action (DESIGN.md §3 "Evaluation of the LSTM student"): the query loop of
 // lstm_train.train without the optimiser steps.  Included inside student_lstm.hip's anonymous
-// namespace after student_lstm_query.h, whose step it runs: the workgroup's layout, the tiling and
+// namespace after student_lstm_query.h and student_lstm_query_bf16.h, whose step it runs: the workgroup's layout, the tiling and
 // the pieces of a step are there.
 //
 // This kernel's own: a workgroup owns its block of 16 envs for the whole launch; an env's state,
@@ -20,7 +20,7 @@ struct LsEvalArgs {
     uint64_t seed;
     const float* tnet;       // teacher net: params | ob mean | ob std
     const float* P;          // the student's flat parameters
-    const float* img;        // lstm_eval_pack_kernel's image of Wl [EV_IMG]
+    const float* img;        // lstm_eval_pack_kernel's image of Wl [EV_IMG]; BF16Q: the bf16 image WF
     const float* draws;      // [E][n][6] or null (Philox)
     const float* state0;     // [2][n][U] = (c, h) or null (zeros)
     float* returns;          // [E][n]
@@ -30,6 +30,8 @@ struct LsEvalArgs {
     int episodes, first_episode, T;
 };
 
+// BF16Q: the positions run on the bf16 cell (student_lstm_query_bf16.h; a.img is then the handle's WF image)
+template <bool BF16Q>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(LsEvalArgs a) {
     const LsThread q = ls_prologue(a.tnet, a.P, a.img, a.T);
     const int tid = q.tid, lane = q.lane, T = q.T;
@@ -66,8 +68,8 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(LsEva
                 lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
                 __syncthreads();
                 ls_teacher(q, s);
-                hp = ls_positions(q, s, hp);
-                ls_head(q, hp);
+                hp = ls_positions_of<BF16Q>(q, s, hp);
+                ls_head<BF16Q>(q, hp);
                 // the next step's first writes (SO, the ring's slot, TO's other parity) follow every
                 // read of them: the barriers above
                 if (phys) {

@@ -11,9 +11,15 @@
 // workgroup: activations stay in LDS between layers, weights stream from L2 as the B
 // operands, and every layer's output is also stored (A1..A4 for the backward, Y).  Same MFMA
 // k order and epilogue (acc + b, tanhf) as the unsplit rd_gemm launches it replaces.
+// FENCE: the chain of a column block in groups of HF_FG k steps whose operands are in registers before
+// the group starts, each group between fence_begin / fence_end (rd_device.h); same MFMAs in the same
+// order.  For a kernel that runs out of registers around the head: the register allocator there renames
+// the chain's accumulator and lets an operand's LDS read or a spilled value's reload land in the SrcC
+// registers it freed while the 8-pass MFMA still reads them (scripts/isa/hazards.py class LDSRC).
+constexpr int HF_FG = 16;
 constexpr int HF_ROWS = 16, HF_MAX_ROWS = 1 << 18;
 constexpr int64_t HPART_MAX_FLOATS = (int64_t)128 << 20;   // the fused head's partial rows: at most 512 MB (reacher_student_lstm.h)
-template <int K, int N, bool TANH, int NW = 4, int LI, int LO>
+template <int K, int N, bool TANH, int NW = 4, bool FENCE = false, int LI, int LO>
 __device__ __forceinline__ void head_layer(const float (*in)[LI], float (*out)[LO], const float* __restrict__ W,
                                            const float* __restrict__ b, float* __restrict__ gout, int ldg,
                                            int64_t row0, int64_t R) {
@@ -26,10 +32,30 @@ __device__ __forceinline__ void head_layer(const float (*in)[LI], float (*out)[L
         const int col = 16 * cb + i;
         const bool cv = col < N;
         rdg::f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (FENCE) {
+            rdg::f32x4 fa[1] = {acc};
 #pragma unroll
-        for (int kq = 0; kq < K / 4; ++kq) {
-            const int k = 4 * kq + gq;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[i][k], cv ? W[k * N + col] : 0.0f, acc, 0, 0, 0);
+            for (int k0 = 0; k0 < K / 4; k0 += HF_FG) {
+                float av[HF_FG], wv[HF_FG];
+#pragma unroll
+                for (int e = 0; e < HF_FG; ++e) {
+                    const int k = 4 * (k0 + e) + gq;
+                    av[e] = k0 + e < K / 4 ? in[i][k] : 0.0f;
+                    wv[e] = k0 + e < K / 4 && cv ? W[k * N + col] : 0.0f;
+                }
+                fence_begin(fa);
+#pragma unroll
+                for (int e = 0; e < HF_FG; ++e)
+                    if (k0 + e < K / 4) fa[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wv[e], fa[0], 0, 0, 0);
+                fence_end(fa);
+            }
+            acc = fa[0];
+        } else {
+#pragma unroll
+            for (int kq = 0; kq < K / 4; ++kq) {
+                const int k = 4 * kq + gq;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[i][k], cv ? W[k * N + col] : 0.0f, acc, 0, 0, 0);
+            }
         }
         const float bv = cv ? b[col] : 0.0f;
 #pragma unroll

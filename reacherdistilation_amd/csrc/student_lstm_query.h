@@ -19,7 +19,9 @@
 //    epilogue);
 //  * head T-1 runs as head_fwd_kernel's five head_layer calls on the final h, over eight waves.
 // The two kernels call these pieces in one order, with the barriers where the pieces say; their
-// bitwise equality with the stepwise path, and with each other, rests on that.
+// bitwise equality with the stepwise path, and with each other, rests on that.  ls_positions is the
+// f32 query's; student_lstm_query_bf16.h holds its sibling on the bf16 cell (rdl_set_query_dtype),
+// which a kernel instance selects by a template argument and which changes nothing else in a step.
 #pragma once
 
 #include "teacher_f32.h"   // namespace tch: the teacher's layouts, load_net and mlp_forward
@@ -272,17 +274,18 @@ __device__ __forceinline__ int ls_positions(const LsThread& q, int s, int hp) {
 }
 
 // Head T-1 on the final h = Hb[hp] into X5 (head_fwd_kernel's layers, a barrier behind each; nothing
-// stored to global: R = 0)
+// stored to global: R = 0).  FENCE: head_layer's (the bf16 instances, which spill around the head).
+template <bool FENCE = false>
 __device__ __forceinline__ void ls_head(const LsThread& q, int hp) {
     const float (*X0)[EV_HS] = lds::Hb[hp];
     uint32_t hoff = 0;   // (opaque, as the image's base: the layers' addresses are formed here)
     asm volatile("" : "+s"(hoff));
     const float* Ph = q.Ph0 + hoff;
-    head_layer<U, H1, true, EV_WAVES>(X0, lds::X1, Ph + OFF_W1, Ph + OFF_B1, nullptr, 0, 0, 0);
-    head_layer<H1, H2, true, EV_WAVES>(lds::X1, lds::X2, Ph + OFF_W2, Ph + OFF_B2, nullptr, 0, 0, 0);
-    head_layer<H2, H3, true, EV_WAVES>(lds::X2, lds::X3, Ph + OFF_W3, Ph + OFF_B3, nullptr, 0, 0, 0);
-    head_layer<H3, H4, true, EV_WAVES>(lds::X3, lds::X4, Ph + OFF_W4, Ph + OFF_B4, nullptr, 0, 0, 0);
-    head_layer<H4, 4, false, EV_WAVES>(lds::X4, lds::X5, Ph + OFF_W5, Ph + OFF_B5, nullptr, 0, 0, 0);
+    head_layer<U, H1, true, EV_WAVES, FENCE>(X0, lds::X1, Ph + OFF_W1, Ph + OFF_B1, nullptr, 0, 0, 0);
+    head_layer<H1, H2, true, EV_WAVES, FENCE>(lds::X1, lds::X2, Ph + OFF_W2, Ph + OFF_B2, nullptr, 0, 0, 0);
+    head_layer<H2, H3, true, EV_WAVES, FENCE>(lds::X2, lds::X3, Ph + OFF_W3, Ph + OFF_B3, nullptr, 0, 0, 0);
+    head_layer<H3, H4, true, EV_WAVES, FENCE>(lds::X3, lds::X4, Ph + OFF_W4, Ph + OFF_B4, nullptr, 0, 0, 0);
+    head_layer<H4, 4, false, EV_WAVES, FENCE>(lds::X4, lds::X5, Ph + OFF_W5, Ph + OFF_B5, nullptr, 0, 0, 0);
 }
 
 // Step s's two pdflats at this lane's env: tp = T_s, sp = the head's row of X5 (no STUDENT: zeros,

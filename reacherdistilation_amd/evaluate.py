@@ -104,7 +104,7 @@ def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, epi
 
 def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, episodes: int, *,
                           n_envs: int | None = None, seed: int = 0, reset: str = "gym", device="cuda:0",
-                          steps: int = STEPS_UNROLLED) -> np.ndarray:
+                          steps: int = STEPS_UNROLLED, dtype: str = "f32", query_dtype: str = "f32") -> np.ndarray:
     """evaluate_student_mlp for the reference's LSTM student: the 50-step returns of its mean action
     over ``episodes`` student-stepped episodes, in one rollout launch (StudentLstmTrainer.evaluate).
     ``trainer_or_params`` is a StudentLstmTrainer (evaluated as it stands, on its device; ``teacher``
@@ -113,7 +113,9 @@ def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, ep
     starts at zero and is carried from query to query over the resets, as the driver carries it, so
     an env's consecutive episodes (n_envs < episodes) are not independent.  Returns a float32 array
     [episodes] in (round, env) order; ``n_envs`` (default: one env per episode), ``seed`` and
-    ``reset`` as evaluate_policy."""
+    ``reset`` as evaluate_policy.  ``dtype`` and ``query_dtype`` are StudentLstmConfig's for the trainer
+    made from a parameter vector (dtype="bf16", query_dtype="bf16": the policy as deployed on the bf16
+    cell); a given trainer is evaluated with its own setting."""
     if reset not in ("gym", "philox"):
         raise ValueError(f"unknown reset mode {reset!r}")
     episodes = int(episodes)
@@ -122,7 +124,8 @@ def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, ep
         raise ValueError("episodes >= 1 and n_envs >= 1")
     E = -(-episodes // n)
     own = not isinstance(trainer_or_params, StudentLstmTrainer)
-    tr = StudentLstmTrainer(StudentLstmConfig(seed=seed, steps=int(steps)), device=device,
+    tr = StudentLstmTrainer(StudentLstmConfig(seed=seed, steps=int(steps), dtype=dtype, query_dtype=query_dtype),
+                            device=device,
                             params=trainer_or_params) if own else trainer_or_params
     try:
         if teacher is not None:

@@ -117,7 +117,7 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-3,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
-               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0):
+               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32"):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -131,7 +131,9 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     window position, 116 KB per window at T = 10: 4.8 MB per env, 1.2 GB at 256 envs, 19 GB at 4,096;
     T x B is at most 2^22 (n_envs <= 10,229 at the defaults).  A few hundred envs is the modest choice.
     ``dtype``: StudentLstmConfig.dtype; with "bf16" the training pass runs the cell matrix's products
-    on the bf16 MFMAs while the envs are still stepped with the f32 master weights.
+    on the bf16 MFMAs while the envs are still stepped with the f32 master weights, unless
+    ``query_dtype`` (StudentLstmConfig.query_dtype) is "bf16" too: the act phase, act_envs and the
+    evaluations then run the cell the training pass trains.
     ``teacher``: an MlpPolicyParams (default: the synthetic teacher DistillTrainer defaults to).
     Returns (trainer, history), history rows (optimiser step, loss, action-MSE, mean step reward) with
     the loss of the trainer's metrics ring (the sum over the batch's T x B rows for "kl"), the
@@ -159,7 +161,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                          "and replay_recent >= 0")
     st = StudentLstmTrainer(StudentLstmConfig(loss=loss, lr=lr, keep_prob=keep_prob, seed=seed, steps=T,
                                               max_windows=Bw if cap else n * (K // 50) * (51 - T),
-                                              metrics_len=steps, dtype=dtype), device=device)
+                                              metrics_len=steps, dtype=dtype, query_dtype=query_dtype), device=device)
     st.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     st.attach_envs(n, seed=seed, accum_steps=K)
     rew = torch.zeros(steps, device=st.device)

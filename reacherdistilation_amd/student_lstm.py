@@ -8,8 +8,11 @@ prev_pdflat [T, B, 4], t_pdflat / pdflat [T, B, 4], state [2, B, 200] = (c, m).
 
 ``StudentLstmConfig(dtype="bf16")`` (rdl_create_dtype) runs the three products of the cell matrix on
 the bf16 MFMAs in forward / rollout / step and the training pass of rollout_envs / step_envs, with
-f32 master weights, heads and sums; evaluate and act_envs stay f32 on the master weights, and the
-checkpoint is the f32 master plus slots either way.
+f32 master weights, heads and sums; the checkpoint is the f32 master plus slots either way.  The
+closed-loop query of evaluate, act_envs and the act phase of rollout_envs / step_envs has its own
+setting, ``query_dtype`` (rdl_set_query_dtype): "f32" (default) keeps it on the f32 master weights,
+"bf16" (bf16 trainers only) runs it on the same bf16 cell as forward, so that one query step is
+bitwise one forward on the env's window and the student that acts is the student that is trained.
 
 Multi-GPU: windows sharded contiguously (row_base = first global window), one
 all_reduce(SUM) of the flat gradient (511,880 floats at T = 10: the shared cell and one
@@ -87,6 +90,8 @@ nat.register({
     "rdl_param_count": (I64, [I32]),
     "rdl_create": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdlConfig), INT, P]),
     "rdl_create_dtype": (INT, [ctypes.POINTER(P), ctypes.POINTER(RdlConfig), I32, INT, P]),
+    "rdl_set_query_dtype": (INT, [P, I32]),
+    "rdl_query_dtype": (INT, [P]),
     "rdl_destroy": (INT, [P]),
     "rdl_set_stream": (INT, [P, P]),
     "rdl_set_params": (INT, [P, P]),
@@ -152,15 +157,33 @@ class StudentLstmConfig:
                                       # gradient) on the bf16 MFMAs in forward / rollout / step and the training
                                       # pass of the envs calls; f32 master, sums, heads; evaluate / act_envs stay
                                       # f32; always the per-step recurrence (step_recurrence has no effect)
+    query_dtype: str = "f32"          # "bf16" (needs dtype="bf16"): the closed-loop query of evaluate / act_envs /
+                                      # the act phase of rollout_envs / step_envs on the bf16 cell too: a query
+                                      # step is bitwise one forward on the env's window
 
     def __post_init__(self):
         self.native_dtype()
+        self.native_query_dtype()
 
     def native_dtype(self) -> int:
         """RDL_DTYPE_* of ``dtype``: what rdl_create_dtype takes."""
         if not isinstance(self.dtype, str) or self.dtype not in DTYPES:
             raise ValueError(f"dtype must be one of {sorted(DTYPES)}, got {self.dtype!r}")
         return DTYPES[self.dtype]
+
+    def native_query_dtype(self) -> int:
+        """RDL_DTYPE_* of ``query_dtype``: what rdl_set_query_dtype takes."""
+        return query_dtype_of(self.query_dtype, self.dtype)
+
+
+def query_dtype_of(name, dtype: str) -> int:
+    """RDL_DTYPE_* of the query dtype ``name`` on a trainer of ``dtype``; ValueError for an unknown name
+    and for "bf16" on an f32 trainer (no bf16 image of Wl, and its training would not match the query)."""
+    if not isinstance(name, str) or name not in DTYPES:
+        raise ValueError(f"query_dtype must be one of {sorted(DTYPES)}, got {name!r}")
+    if name == "bf16" and dtype != "bf16":
+        raise ValueError(f'query_dtype="bf16" requires dtype="bf16", got dtype={dtype!r}')
+    return DTYPES[name]
 
 
 class StudentLstmTrainer:
@@ -173,6 +196,7 @@ class StudentLstmTrainer:
         self.rank, self.world, self.pg = rank, world_size, process_group
         self.T = int(self.cfg.steps)
         dtype = self.cfg.native_dtype()   # a bad dtype raises before any native call
+        qdtype = self.cfg.native_query_dtype()
         self._lib = nat.load()
         self.n_params = n_params(self.T)
         assert self._lib.rdl_param_count(self.T) == self.n_params
@@ -186,6 +210,7 @@ class StudentLstmTrainer:
             nat.check(self._lib.rdl_create_dtype(ctypes.byref(h), ctypes.byref(c), dtype, self.device.index or 0,
                                                  nat.stream_handle(self.device)), "rdl_create_dtype")
         self._h = h
+        nat.check(self._lib.rdl_set_query_dtype(self._h, qdtype), "rdl_set_query_dtype")
         self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._envs = None     # attach_envs()'s buffers
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
@@ -224,6 +249,20 @@ class StudentLstmTrainer:
         nat.check(self._lib.rdl_set_teacher(self._h, nat.ptr(f), nat.ptr(mu), nat.ptr(sd)), "rdl_set_teacher")
         torch.cuda.current_stream(self.device).synchronize()
         self.teacher = p
+
+    def set_query_dtype(self, name: str):
+        """The arithmetic of the closed-loop query (evaluate, act_envs, the act phase of rollout_envs /
+        step_envs) from the next call on: "f32", the master weights, or "bf16" on a dtype="bf16" trainer,
+        the bf16 cell of forward (rdl_set_query_dtype; host-only).  A refused name leaves the setting."""
+        nat.check(self._lib.rdl_set_query_dtype(self._h, query_dtype_of(name, self.cfg.dtype)), "rdl_set_query_dtype")
+
+    @property
+    def query_dtype(self) -> str:
+        """"f32" or "bf16": what the handle's closed-loop query runs in (rdl_query_dtype)."""
+        r = self._lib.rdl_query_dtype(self._h)
+        if r < 0:
+            raise RuntimeError("query_dtype: the trainer is closed")
+        return next(k for k, v in DTYPES.items() if v == r)
 
     @property
     def fused_head(self) -> bool:
@@ -341,7 +380,8 @@ class StudentLstmTrainer:
         unclipped mean of unrolled position T-1 steps the env.  Bitwise the stepwise loop --
         BatchedReacher.reset(), then 50 x {DistillTrainer.forward (teacher), the windows,
         forward(ob_w, prev_w, state)[T-1], BatchedReacher.step(mean)} per episode -- with no side
-        effect on the trainer.  Episode e of env i resets from ``draws[e, i]`` ([E, n_envs, 6]) or,
+        effect on the trainer (on a bf16 trainer: this trainer's loop under query_dtype="bf16", an f32
+        trainer's with the same parameters under the default "f32").  Episode e of env i resets from ``draws[e, i]`` ([E, n_envs, 6]) or,
         without a table, from Philox(seed, env_base + i, first_episode + e).  Returns a
         distill.EvalResult: returns [E, n]; final_dist [E, n]; records [E, n, 50, 21] in the dataset's
         layout (stepped_with = 1); state [2, n, 200] = (c, h) after the last query with
