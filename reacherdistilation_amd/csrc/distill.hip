@@ -32,6 +32,7 @@
 #include "../../include/reacher_distill.h"
 #include "rd_comm_impl.h"
 #include "rd_common.h"
+#include "rd_host.h"
 #include "rd_device.h"
 #include "rd_physics.h"
 
@@ -77,6 +78,7 @@ struct rdd_trainer {
     int device = 0;
     hipStream_t stream = nullptr;
     int grid = 0;
+    rd::DeviceAllocs mem;      // every device buffer below
     float* state = nullptr;    // [8][n]
     float* tnet = nullptr;     // [P + 22]
     float* snet = nullptr;     // [P + 22]
@@ -268,27 +270,25 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
     t->last_grid = t->grid;
     t->last_gs = t->gs;
     const size_t netf = P_TOT + 2 * OBD;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, t->stream);
-    };
-    alloc((void**)&t->state, sizeof(float) * 8 * cfg->n_envs);
-    alloc((void**)&t->tnet, sizeof(float) * netf);
-    alloc((void**)&t->snet, sizeof(float) * netf);
-    alloc((void**)&t->timg, sizeof(float) * image_floats(teacher_kind(t), false));
-    alloc((void**)&t->simg, sizeof(float) * image_floats(student_kind(t), true));
-    alloc((void**)&t->m, sizeof(float) * P_TOT);
-    alloc((void**)&t->v, sizeof(float) * P_TOT);
-    alloc((void**)&t->own_grad, sizeof(float) * P_TOT);
+    rd::DeviceAllocs& mem = t->mem;
+    mem.stream = t->stream;
+    mem.zeroed(&t->state, (size_t)8 * cfg->n_envs);
+    mem.zeroed(&t->tnet, netf);
+    mem.zeroed(&t->snet, netf);
+    mem.zeroed(&t->timg, image_floats(teacher_kind(t), false));
+    mem.zeroed(&t->simg, image_floats(student_kind(t), true));
+    mem.zeroed(&t->m, P_TOT);
+    mem.zeroed(&t->v, P_TOT);
+    mem.zeroed(&t->own_grad, P_TOT);
     t->grad = t->own_grad;
-    alloc((void**)&t->ws, sizeof(float) * (size_t)t->ws_rows * P_WS);
-    alloc((void**)&t->hist, sizeof(float) * (size_t)t->cfg.metrics_len * N_MET);
-    alloc((void**)&t->ctl, sizeof(uint32_t) * 16);
+    mem.zeroed(&t->ws, (size_t)t->ws_rows * P_WS);
+    mem.zeroed(&t->hist, (size_t)t->cfg.metrics_len * N_MET);
+    mem.zeroed(&t->ctl, 16);
 #ifdef RD_STAMPS
-    alloc((void**)&t->dbg, sizeof(unsigned long long) * (size_t)t->ws_rows * WAVES * NSTAMP);
+    mem.zeroed(&t->dbg, (size_t)t->ws_rows * WAVES * NSTAMP);
 #endif
-    if (e != hipSuccess) {
+    if (mem.err != hipSuccess) {
+        const hipError_t e = mem.err;
         rdd_destroy(t);
         return rd::hip_fail(e, "rdd_create: allocation");
     }
@@ -299,9 +299,7 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
 int rdd_destroy(rdd_trainer* t) {
     if (!t) return RD_OK;
     rd::DeviceGuard g(t->device);
-    for (void* p : {(void*)t->state, (void*)t->tnet, (void*)t->snet, (void*)t->m, (void*)t->v, (void*)t->own_grad,
-                    (void*)t->ws, (void*)t->hist, (void*)t->ctl, (void*)t->dbg, (void*)t->timg, (void*)t->simg})
-        if (p) (void)hipFree(p);
+    t->mem.free_all();
     delete t;
     return RD_OK;
 }
@@ -311,9 +309,7 @@ static int set_net(rdd_trainer* t, float* dst, const float* params, const float*
     if (!t || !params || !mu || !sd) return rd::set_error(RD_EINVAL, "%s: null argument", what);
     rd::DeviceGuard g(t->device);
     RD_HIP(g.err, what);
-    RD_HIP(hipMemcpyAsync(dst, params, sizeof(float) * P_TOT, hipMemcpyDeviceToDevice, t->stream), what);
-    RD_HIP(hipMemcpyAsync(dst + P_TOT, mu, sizeof(float) * OBD, hipMemcpyDeviceToDevice, t->stream), what);
-    RD_HIP(hipMemcpyAsync(dst + P_TOT + OBD, sd, sizeof(float) * OBD, hipMemcpyDeviceToDevice, t->stream), what);
+    if (int rc = rd::upload_net(what, dst, params, P_TOT, mu, sd, OBD, t->stream)) return rc;
     const bool student = dst == t->snet;
     const int kind = student ? student_kind(t) : teacher_kind(t);
     hipLaunchKernelGGL(pack_net_kernel, dim3(1), dim3(256), 0, t->stream, dst, student ? t->simg : t->timg,
@@ -333,6 +329,7 @@ int rdd_set_student(rdd_trainer* t, const float* p, const float* mu, const float
 int rdd_get_student(rdd_trainer* t, float* params) {
     if (!t || !params) return rd::set_error(RD_EINVAL, "rdd_get_student: null argument");
     rd::DeviceGuard g(t->device);
+    RD_HIP(g.err, "rdd_get_student");
     RD_HIP(hipMemcpyAsync(params, t->snet, sizeof(float) * P_TOT, hipMemcpyDeviceToDevice, t->stream),
            "rdd_get_student");
     return RD_OK;
@@ -543,6 +540,7 @@ int rdd_evaluate(rdd_trainer* t, const rdd_eval_config* cfg, float* returns, flo
 int rdd_get_env_state(rdd_trainer* t, float* state) {
     if (!t || !state) return rd::set_error(RD_EINVAL, "rdd_get_env_state: null argument");
     rd::DeviceGuard g(t->device);
+    RD_HIP(g.err, "rdd_get_env_state");
     RD_HIP(hipMemcpyAsync(state, t->state, sizeof(float) * 8 * t->cfg.n_envs, hipMemcpyDeviceToDevice, t->stream),
            "rdd_get_env_state");
     return RD_OK;
@@ -551,6 +549,7 @@ int rdd_get_env_state(rdd_trainer* t, float* state) {
 int rdd_set_env_state(rdd_trainer* t, const float* state) {
     if (!t || !state) return rd::set_error(RD_EINVAL, "rdd_set_env_state: null argument");
     rd::DeviceGuard g(t->device);
+    RD_HIP(g.err, "rdd_set_env_state");
     // the caller's angles are checked before they replace the trainer's (ctl[14]: this check's flag)
     const int64_t n = t->cfg.n_envs;
     uint32_t bad = 0;
@@ -572,6 +571,7 @@ int rdd_set_env_state(rdd_trainer* t, const float* state) {
 
 static int read_ctl(rdd_trainer* t, uint32_t (&c)[16], const char* what) {
     rd::DeviceGuard g(t->device);
+    RD_HIP(g.err, what);
     RD_HIP(hipMemcpyAsync(c, t->ctl, sizeof(c), hipMemcpyDeviceToHost, t->stream), what);
     RD_HIP(hipStreamSynchronize(t->stream), what);
     if (c[8]) return rd::set_error(RD_EINVAL, "%s: a rollout's producer/consumer hand-off timed out", what);
@@ -600,22 +600,7 @@ int rdd_read_metrics(rdd_trainer* t, int64_t count, double* out) {
     if (!t || !out || count < 0) return rd::set_error(RD_EINVAL, "rdd_read_metrics: bad argument");
     int64_t steps = 0;   // metrics are kept per optimiser step
     if (int rc = rdd_get_counters(t, nullptr, &steps)) return rc;
-    const int64_t H = t->cfg.metrics_len;
-    if (count > steps || count > H) return rd::set_error(RD_EINVAL, "rdd_read_metrics: only %lld steps kept",
-                                                         (long long)(steps < H ? steps : H));
-    float* host = new (std::nothrow) float[(size_t)H * N_MET];
-    if (!host) return rd::set_error(RD_EINVAL, "rdd_read_metrics: out of host memory");
-    hipError_t e = hipMemcpy(host, t->hist, sizeof(float) * H * N_MET, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        delete[] host;
-        return rd::hip_fail(e, "rdd_read_metrics");
-    }
-    for (int64_t k = 0; k < count; ++k) {
-        const int64_t s = (steps - count + k) % H;
-        for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
-    }
-    delete[] host;
-    return RD_OK;
+    return rd::read_ring("rdd_read_metrics", "steps", t->hist, t->cfg.metrics_len, N_MET, steps, count, out);
 }
 
 int rdd_last_layout(const rdd_trainer* t, int32_t out[4]) {

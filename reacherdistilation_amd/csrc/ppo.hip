@@ -26,6 +26,7 @@
 
 #include "../../include/reacher_ppo.h"
 #include "rd_common.h"
+#include "rd_host.h"
 #include "rd_device.h"
 #include "rd_physics.h"
 
@@ -776,6 +777,7 @@ struct rdp_trainer {
     rdp_config cfg{};
     int device = 0, cus = 256;
     hipStream_t stream = nullptr;
+    rd::DeviceAllocs mem;   // every device buffer of the handle
     int64_t n = 0, S = 0;
     int mb = 0;
     uint32_t iter = 0;
@@ -931,18 +933,11 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
     t->mb = cfg->optim_batchsize > 0 ? cfg->optim_batchsize : (int)S;
     for (auto& h : t->host_perm) h.resize((size_t)cfg->optim_epochs * S);
     const int64_t n = t->n;
-    hipError_t e = hipSuccess;
-    auto af = [&](float** p, int64_t cnt) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, sizeof(float) * (size_t)(cnt > 0 ? cnt : 1));
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, sizeof(float) * (size_t)(cnt > 0 ? cnt : 1), t->stream);
-    };
-    auto ai = [&](int** p, int64_t cnt) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, sizeof(int) * (size_t)cnt);
-    };
-    auto ad = [&](double** p, int64_t cnt) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, sizeof(double) * (size_t)cnt);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, sizeof(double) * (size_t)cnt, t->stream);
-    };
+    rd::DeviceAllocs& mem = t->mem;
+    mem.stream = t->stream;
+    auto af = [&](float** p, int64_t cnt) { mem.zeroed(p, (size_t)(cnt > 0 ? cnt : 1)); };
+    auto ai = [&](int** p, int64_t cnt) { mem.raw(p, (size_t)cnt); };
+    auto ad = [&](double** p, int64_t cnt) { mem.zeroed(p, (size_t)cnt); };
     af(&t->params, P_ALL); af(&t->m, P_ALL); af(&t->v, P_ALL); af(&t->own_grad, P_ALL);
     t->grad = t->own_grad;
     af(&t->state, 8 * n); af(&t->ep_ret, n); af(&t->new_next, n); af(&t->it_ret, n); af(&t->it_eps, n);
@@ -959,8 +954,9 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
     af(&t->mbpart, (int64_t)MB_G * PSTR);
     ad(&t->mbstat, (int64_t)MB_G * NSTAT);
     af(&t->hist, (int64_t)t->cfg.metrics_len * N_MET);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->ctl, sizeof(uint32_t) * 8);
-    if (e != hipSuccess) {
+    mem.raw(&t->ctl, 8);
+    if (mem.err != hipSuccess) {
+        const hipError_t e = mem.err;
         rdp_destroy(t);
         return rd::hip_fail(e, "rdp_create: allocation");
     }
@@ -975,12 +971,7 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
 int rdp_destroy(rdp_trainer* t) {
     if (!t) return RD_OK;
     rd::DeviceGuard dg(t->device);
-    void* bufs[] = {t->params, t->m, t->v, t->own_grad, t->state, t->ep_ret, t->new_next, t->it_ret, t->it_eps,
-                    t->ep_step, t->ep_idx, t->ob, t->ac, t->vpred, t->rew, t->newf, t->nextv, t->adv, t->ret,
-                    t->atarg, t->lpo, t->rms_sums, t->part, t->stats, t->acc, t->rms, t->perm, t->mbpart,
-                    t->mbstat, t->hist, t->ctl};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    t->mem.free_all();
     delete t;
     return RD_OK;
 }
@@ -994,6 +985,7 @@ int rdp_set_stream(rdp_trainer* t, void* hip_stream) {
 static int copy_params(rdp_trainer* t, float* dst, const float* src, int count, const char* what) {
     if (!t || !src || !dst) return rd::set_error(RD_EINVAL, "%s: null argument", what);
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, what);
     RD_HIP(hipMemcpyAsync(dst, src, sizeof(float) * count, hipMemcpyDeviceToDevice, t->stream), what);
     return RD_OK;
 }
@@ -1012,6 +1004,7 @@ int rdp_get_value(rdp_trainer* t, float* p) {
 int rdp_get_obfilter(rdp_trainer* t, float* mean, float* std) {
     if (!t || !mean || !std) return rd::set_error(RD_EINVAL, "rdp_get_obfilter: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_get_obfilter");
     hipLaunchKernelGGL(rms_finalize_kernel, dim3(1), dim3(64), 0, t->stream, (const double*)t->rms_sums, t->rms);
     RD_HIP(hipMemcpyAsync(mean, t->rms, sizeof(float) * OBD, hipMemcpyDeviceToDevice, t->stream), "rdp_get_obfilter");
     RD_HIP(hipMemcpyAsync(std, t->rms + OBD, sizeof(float) * OBD, hipMemcpyDeviceToDevice, t->stream),
@@ -1059,6 +1052,7 @@ int rdp_get_batch(rdp_trainer* t, float* ob, float* ac, float* vpred, float* rew
                   float* adv, float* ret) {
     if (!t) return rd::set_error(RD_EINVAL, "rdp_get_batch: null handle");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_get_batch");
     const int64_t S = t->S;
     struct {
         float* dst;
@@ -1089,18 +1083,11 @@ int rdp_get_counter(rdp_trainer* t, int64_t* iterations) {
 
 int rdp_read_metrics(rdp_trainer* t, int64_t count, double* out) {
     if (!t || !out || count < 0) return rd::set_error(RD_EINVAL, "rdp_read_metrics: bad argument");
-    const int64_t H = t->cfg.metrics_len, it = t->iter;
-    if (count > it || count > H)
-        return rd::set_error(RD_EINVAL, "rdp_read_metrics: only %lld iterations kept", (long long)(it < H ? it : H));
     rd::DeviceGuard dg(t->device);
-    std::vector<float> host((size_t)H * N_MET);
+    RD_HIP(dg.err, "rdp_read_metrics");
+    // the iteration count is the host's, so the ring is read behind the stream's work
     RD_HIP(hipStreamSynchronize(t->stream), "rdp_read_metrics");
-    RD_HIP(hipMemcpy(host.data(), t->hist, sizeof(float) * H * N_MET, hipMemcpyDeviceToHost), "rdp_read_metrics");
-    for (int64_t k = 0; k < count; ++k) {
-        const int64_t s = (it - count + k) % H;
-        for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
-    }
-    return RD_OK;
+    return rd::read_ring("rdp_read_metrics", "iterations", t->hist, t->cfg.metrics_len, N_MET, t->iter, count, out);
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@
 #include "rd_common.h"
 #include "rd_device.h"
 #include "rd_gemm.h"
+#include "rd_host.h"
 #include "rd_physics.h"
 
 namespace {
@@ -96,15 +97,12 @@ struct rdl_trainer {
     int64_t last_B = 0;   // windows of the last forward pass (rdl_final_state)
     float* tnet = nullptr;     // rdl_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
     float* eimg = nullptr;     // rdl_evaluate's packed image of Wl [EV_IMG], rebuilt by every call
+    rd::DeviceAllocs mem;      // every device buffer of the handle but the envs'
     bool has_teacher = false;
     // the persistent envs (rdl_envs_attach)
-    float *env_state = nullptr, *env_aux = nullptr;   // [8][n] SoA; [ENV_AUX][n]
-    int32_t* env_clock = nullptr;                     // [2][n]: step of the episode, episode
+    rd::EnvBufs envs;                                 // state [8][n] SoA, aux [ENV_AUX][n], clock [2][n]
     float* env_q = nullptr;                           // [2][n][U] = (c, h) of the envs' last query
     float* env_hist = nullptr;                        // [n][T][EH_REC]: the raw fields of the ring's records
-    int64_t envs_n = 0, envs_base = 0;
-    uint64_t envs_seed = 0;
-    int envs_grid = 0;
     // RDL_DTYPE_BF16 (student_lstm_bf16.h): the bf16 images of Wl (forward, then transposed) and the
     // weight gradient's split-K partials [wsplits][243][800]; both null on an f32 handle
     int dtype = RDL_DTYPE_F32;
@@ -553,23 +551,23 @@ int launch_eval_pack(rdl_trainer* t) {
 
 // ---------------------------------------------------------------- persistent envs
 void free_envs(rdl_trainer* t) {
-    for (void* p : {(void*)t->env_state, (void*)t->env_aux, (void*)t->env_clock, (void*)t->env_q, (void*)t->env_hist})
+    t->envs.release();
+    for (float* p : {t->env_q, t->env_hist})
         if (p) (void)hipFree(p);
-    t->env_state = t->env_aux = t->env_q = t->env_hist = nullptr;
-    t->env_clock = nullptr;
+    t->env_q = t->env_hist = nullptr;
 }
 
 LsEnvsArgs envs_args(const rdl_trainer* t) {
     LsEnvsArgs a{};
-    a.n = t->envs_n;
-    a.env_base = t->envs_base;
-    a.seed = t->envs_seed;
+    a.n = t->envs.n;
+    a.env_base = t->envs.base;
+    a.seed = t->envs.seed;
     a.tnet = t->tnet;
     a.P = t->params;
     a.img = bf16_query(t) ? (const float*)t->wimg : t->eimg;
-    a.state = t->env_state;
-    a.aux = t->env_aux;
-    a.clock = t->env_clock;
+    a.state = t->envs.state;
+    a.aux = t->envs.aux;
+    a.clock = t->envs.clock;
     a.q = t->env_q;
     a.hist = t->env_hist;
     a.T = t->T;
@@ -589,13 +587,13 @@ int envs_check(const char* fn, const rdl_trainer* t, int act_with, int steps, co
     if (train ? !ob_w || !prev_w || !t_w : (ob_w || prev_w || t_w) && (!ob_w || !prev_w || !t_w))
         return rd::set_error(RD_EINVAL, "%s: null ob_w, prev_w or t_w (the window buffers go together)", fn);
     if (!train && ob_w && *B < 1) return rd::set_error(RD_EINVAL, "%s: windows %lld < 1", fn, (long long)*B);
-    if (!t->env_state) return rd::set_error(RD_EINVAL, "%s: no envs attached (rdl_envs_attach)", fn);
+    if (!t->envs.state) return rd::set_error(RD_EINVAL, "%s: no envs attached (rdl_envs_attach)", fn);
     if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdl_set_teacher)", fn);
     if (t->T > EV_MAX_T)
         return rd::set_error(RD_EINVAL, "%s: rdl_config.steps = %d unrolled steps, the kernel keeps at most %d records "
                                         "of history", fn, t->T, EV_MAX_T);
-    if (t->envs_n > ((int64_t)1 << 31) / steps)
-        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs_n);
+    if (t->envs.n > ((int64_t)1 << 31) / steps)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs.n);
     if (train) {
         if (steps % rd::kEpisodeSteps)
             return rd::set_error(RD_EINVAL, "%s: steps %d is not a multiple of the episode's %d", fn, steps,
@@ -603,7 +601,7 @@ int envs_check(const char* fn, const rdl_trainer* t, int act_with, int steps, co
         if (t->T > rd::kEpisodeSteps)
             return rd::set_error(RD_EINVAL, "%s: rdl_config.steps = %d exceeds the episode's %d steps", fn, t->T,
                                  rd::kEpisodeSteps);
-        *B = t->envs_n * (steps / rd::kEpisodeSteps) * (rd::kEpisodeSteps + 1 - t->T);
+        *B = t->envs.n * (steps / rd::kEpisodeSteps) * (rd::kEpisodeSteps + 1 - t->T);
         if (*B > t->Bmax)
             return rd::set_error(RD_EINVAL, "%s: %lld windows > rdl_config.max_windows = %lld", fn, (long long)*B,
                                  (long long)t->Bmax);
@@ -626,7 +624,7 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     a.t_w = t_w;
     a.windows = ob_w ? B : 0;
     a.steps = steps;
-    const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = t->envs_grid > 0 ? t->envs_grid : t->cus;
+    const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = t->envs.grid > 0 ? t->envs.grid : t->cus;
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
     auto* kern = !stu ? student_lstm_envs_kernel<false, false>
                  : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
@@ -682,55 +680,52 @@ int rdl_create_dtype(rdl_trainer** out, const rdl_config* cfg, int32_t dtype, in
     const int64_t R = (int64_t)t->T * t->Bmax, B = t->Bmax;
     const int64_t nch = (R + COLSUM_CHUNK - 1) / COLSUM_CHUNK;
     t->colws_floats = nch * G4;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](float** p, int64_t floats) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, sizeof(float) * (size_t)floats);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, sizeof(float) * (size_t)floats, t->stream);
-    };
-    alloc(&t->params, t->np);
-    alloc(&t->m, t->np);
-    alloc(&t->v, t->np);
-    alloc(&t->own_grad, t->np);
-    alloc(&t->X, R * XLD);
-    alloc(&t->H, (R + B) * U);
-    alloc(&t->Cs, (R + B) * U);
-    alloc(&t->Z, R * G4);
-    alloc(&t->G, R * G4);
-    alloc(&t->A1, R * L1);
-    alloc(&t->A2, R * L2);
-    alloc(&t->A3, R * L3);
-    alloc(&t->A4, R * L4);
-    alloc(&t->Y, R * 4);
-    alloc(&t->dY, R * 4);
-    alloc(&t->D32, R * H4);
-    alloc(&t->D64a, R * H3);
-    alloc(&t->D128, R * H2);
-    alloc(&t->D64b, R * H1);
-    alloc(&t->dHh, R * U);
-    alloc(&t->dP, R * 32);
-    alloc(&t->dhn, B * U);
-    alloc(&t->dc, B * U);
-    alloc(&t->split, SPLIT_FLOATS);
+    rd::DeviceAllocs& mem = t->mem;
+    mem.stream = t->stream;
+    mem.zeroed(&t->params, t->np);
+    mem.zeroed(&t->m, t->np);
+    mem.zeroed(&t->v, t->np);
+    mem.zeroed(&t->own_grad, t->np);
+    mem.zeroed(&t->X, R * XLD);
+    mem.zeroed(&t->H, (R + B) * U);
+    mem.zeroed(&t->Cs, (R + B) * U);
+    mem.zeroed(&t->Z, R * G4);
+    mem.zeroed(&t->G, R * G4);
+    mem.zeroed(&t->A1, R * L1);
+    mem.zeroed(&t->A2, R * L2);
+    mem.zeroed(&t->A3, R * L3);
+    mem.zeroed(&t->A4, R * L4);
+    mem.zeroed(&t->Y, R * 4);
+    mem.zeroed(&t->dY, R * 4);
+    mem.zeroed(&t->D32, R * H4);
+    mem.zeroed(&t->D64a, R * H3);
+    mem.zeroed(&t->D128, R * H2);
+    mem.zeroed(&t->D64b, R * H1);
+    mem.zeroed(&t->dHh, R * U);
+    mem.zeroed(&t->dP, R * 32);
+    mem.zeroed(&t->dhn, B * U);
+    mem.zeroed(&t->dc, B * U);
+    mem.zeroed(&t->split, SPLIT_FLOATS);
     int64_t nbmax = 0;   // the most workgroups of any batch up to Bmax (head_nb is not monotone)
     for (int64_t b = HF_ROWS; b < t->Bmax + HF_ROWS; b += HF_ROWS) nbmax = std::max<int64_t>(nbmax, head_nb(t->T, b));
     const int64_t hp = (int64_t)t->T * nbmax * HB_PART;
-    if (hp <= HPART_MAX_FLOATS) alloc(&t->hpart, hp);
-    alloc(&t->wpack, (int64_t)t->T * HWP);
-    alloc(&t->colws, t->colws_floats);
-    alloc(&t->lpart, std::max<int64_t>(2 * ((R + LOSS_BLOCK - 1) / LOSS_BLOCK), 2 * HB_WIDE_GRID));
-    alloc(&t->hist, (int64_t)t->cfg.metrics_len * N_MET);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->ctl, sizeof(uint32_t) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->bar, sizeof(uint32_t) * 4);
-    alloc(&t->bpart, (int64_t)2 * PR_GRID * PB_PART);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->hx, sizeof(unsigned long long) * 2 * PR_ROWS * U);
-    if (e == hipSuccess) e = hipMemsetAsync(t->hx, 0, sizeof(unsigned long long) * 2 * PR_ROWS * U, t->stream);
-    alloc(&t->qbuf, 4 * G4);
-    alloc(&t->tnet, tch::P_TOT + 2 * tch::OBD);
-    alloc(&t->eimg, EV_IMG);
+    if (hp <= HPART_MAX_FLOATS) mem.zeroed(&t->hpart, hp);
+    mem.zeroed(&t->wpack, (int64_t)t->T * HWP);
+    mem.zeroed(&t->colws, t->colws_floats);
+    mem.zeroed(&t->lpart, std::max<int64_t>(2 * ((R + LOSS_BLOCK - 1) / LOSS_BLOCK), 2 * HB_WIDE_GRID));
+    mem.zeroed(&t->hist, (int64_t)t->cfg.metrics_len * N_MET);
+    mem.raw(&t->ctl, 8);
+    mem.raw(&t->bar, 4);
+    mem.zeroed(&t->bpart, (int64_t)2 * PR_GRID * PB_PART);
+    mem.zeroed(&t->hx, (size_t)2 * PR_ROWS * U);
+    mem.zeroed(&t->qbuf, 4 * G4);
+    mem.zeroed(&t->tnet, tch::P_TOT + 2 * tch::OBD);
+    mem.zeroed(&t->eimg, EV_IMG);
     if (bf16_cell(t)) {
-        if (e == hipSuccess) e = hipMalloc((void**)&t->wimg, sizeof(bf16x8) * BF_IMG_GROUPS);
-        alloc(&t->wpart, std::min<int64_t>(BF_WG_SPLITS, (R + BF_WG_CHUNK - 1) / BF_WG_CHUNK) * BF_KWL * G4);
+        mem.raw(&t->wimg, BF_IMG_GROUPS);
+        mem.zeroed(&t->wpart, std::min<int64_t>(BF_WG_SPLITS, (R + BF_WG_CHUNK - 1) / BF_WG_CHUNK) * BF_KWL * G4);
     }
+    hipError_t e = mem.err;
     if (e == hipSuccess) e = hipMemsetAsync(t->bar, 0, sizeof(uint32_t) * 4, t->stream);
     t->grad = t->own_grad;
     if (e != hipSuccess) {
@@ -777,17 +772,8 @@ int rdl_query_dtype(const rdl_trainer* t) { return t ? t->qdtype : -1; }
 int rdl_destroy(rdl_trainer* t) {
     if (!t) return RD_OK;
     rd::DeviceGuard dg(t->device);
-    float* bufs[] = {t->params, t->m, t->v, t->own_grad, t->X, t->H, t->Cs, t->Z, t->G, t->A1, t->A2, t->A3, t->A4,
-                     t->Y, t->dY, t->D32, t->D64a, t->D128, t->D64b, t->dHh, t->dP, t->dhn, t->dc, t->split,
-                     t->colws, t->lpart, t->hist, t->bpart, t->qbuf, t->hpart, t->wpack, t->tnet, t->eimg,
-                     t->wpart};
-    for (float* p : bufs)
-        if (p) (void)hipFree(p);
+    t->mem.free_all();
     free_envs(t);
-    if (t->hx) (void)hipFree(t->hx);
-    if (t->wimg) (void)hipFree(t->wimg);
-    if (t->ctl) (void)hipFree(t->ctl);
-    if (t->bar) (void)hipFree(t->bar);
     delete t;
     return RD_OK;
 }
@@ -801,6 +787,7 @@ int rdl_set_stream(rdl_trainer* t, void* hip_stream) {
 int rdl_set_params(rdl_trainer* t, const float* params) {
     if (!t || !params) return rd::set_error(RD_EINVAL, "rdl_set_params: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_set_params");
     RD_HIP(hipMemcpyAsync(t->params, params, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream),
            "rdl_set_params");
     const int64_t n = (int64_t)t->T * HSZ;
@@ -813,6 +800,7 @@ int rdl_set_params(rdl_trainer* t, const float* params) {
 int rdl_get_params(rdl_trainer* t, float* params) {
     if (!t || !params) return rd::set_error(RD_EINVAL, "rdl_get_params: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_get_params");
     RD_HIP(hipMemcpyAsync(params, t->params, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream),
            "rdl_get_params");
     return RD_OK;
@@ -821,6 +809,7 @@ int rdl_get_params(rdl_trainer* t, float* params) {
 int rdl_get_slots(rdl_trainer* t, float* m, float* v) {
     if (!t || !m || !v) return rd::set_error(RD_EINVAL, "rdl_get_slots: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_get_slots");
     RD_HIP(hipMemcpyAsync(m, t->m, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream), "rdl_get_slots");
     RD_HIP(hipMemcpyAsync(v, t->v, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream), "rdl_get_slots");
     return RD_OK;
@@ -829,6 +818,7 @@ int rdl_get_slots(rdl_trainer* t, float* m, float* v) {
 int rdl_set_slots(rdl_trainer* t, const float* m, const float* v) {
     if (!t || !m || !v) return rd::set_error(RD_EINVAL, "rdl_set_slots: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_set_slots");
     RD_HIP(hipMemcpyAsync(t->m, m, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream), "rdl_set_slots");
     RD_HIP(hipMemcpyAsync(t->v, v, sizeof(float) * t->np, hipMemcpyDeviceToDevice, t->stream), "rdl_set_slots");
     return RD_OK;
@@ -837,6 +827,7 @@ int rdl_set_slots(rdl_trainer* t, const float* m, const float* v) {
 int rdl_reset(rdl_trainer* t) {
     if (!t) return rd::set_error(RD_EINVAL, "rdl_reset: null handle");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_reset");
     RD_HIP(hipMemsetAsync(t->m, 0, sizeof(float) * t->np, t->stream), "rdl_reset");
     RD_HIP(hipMemsetAsync(t->v, 0, sizeof(float) * t->np, t->stream), "rdl_reset");
     hipLaunchKernelGGL(init_ctl_kernel, dim3(1), dim3(64), 0, t->stream, t->ctl, t->cfg.beta1, t->cfg.beta2);
@@ -901,6 +892,7 @@ int rdl_head_path(const rdl_trainer* t) {
 int rdl_get_counter(rdl_trainer* t, int64_t* opt_steps) {
     if (!t || !opt_steps) return rd::set_error(RD_EINVAL, "rdl_get_counter: null argument");
     rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdl_get_counter");
     uint32_t c[8], b[4];
     RD_HIP(hipMemcpyAsync(c, t->ctl, sizeof(c), hipMemcpyDeviceToHost, t->stream), "rdl_get_counter");
     RD_HIP(hipMemcpyAsync(b, t->bar, sizeof(b), hipMemcpyDeviceToHost, t->stream), "rdl_get_counter");
@@ -916,34 +908,15 @@ int rdl_read_metrics(rdl_trainer* t, int64_t count, double* out) {
     if (!t || !out || count < 0) return rd::set_error(RD_EINVAL, "rdl_read_metrics: bad argument");
     int64_t steps = 0;
     if (int rc = rdl_get_counter(t, &steps)) return rc;
-    const int64_t Hn = t->cfg.metrics_len;
-    if (count > steps || count > Hn)
-        return rd::set_error(RD_EINVAL, "rdl_read_metrics: only %lld steps kept", (long long)(steps < Hn ? steps : Hn));
-    float* host = new (std::nothrow) float[(size_t)Hn * N_MET];
-    if (!host) return rd::set_error(RD_EINVAL, "rdl_read_metrics: out of host memory");
-    hipError_t e = hipMemcpy(host, t->hist, sizeof(float) * Hn * N_MET, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        delete[] host;
-        return rd::hip_fail(e, "rdl_read_metrics");
-    }
-    for (int64_t k = 0; k < count; ++k) {
-        const int64_t s = (steps - count + k) % Hn;
-        for (int j = 0; j < N_MET; ++j) out[k * N_MET + j] = host[s * N_MET + j];
-    }
-    delete[] host;
-    return RD_OK;
+    return rd::read_ring("rdl_read_metrics", "steps", t->hist, t->cfg.metrics_len, N_MET, steps, count, out);
 }
 
 int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, const float* ob_std) {
     if (!t || !params || !ob_mean || !ob_std) return rd::set_error(RD_EINVAL, "rdl_set_teacher: null argument");
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdl_set_teacher");
-    RD_HIP(hipMemcpyAsync(t->tnet, params, sizeof(float) * tch::P_TOT, hipMemcpyDeviceToDevice, t->stream),
-           "rdl_set_teacher");
-    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT, ob_mean, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice, t->stream),
-           "rdl_set_teacher");
-    RD_HIP(hipMemcpyAsync(t->tnet + tch::P_TOT + tch::OBD, ob_std, sizeof(float) * tch::OBD, hipMemcpyDeviceToDevice,
-                          t->stream), "rdl_set_teacher");
+    if (int rc = rd::upload_net("rdl_set_teacher", t->tnet, params, tch::P_TOT, ob_mean, ob_std, tch::OBD, t->stream))
+        return rc;
     t->has_teacher = true;
     return RD_OK;
 }
@@ -989,45 +962,34 @@ int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0
 
 int rdl_envs_reset(rdl_trainer* t) {
     if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_reset: null trainer");
-    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_reset: no envs attached (rdl_envs_attach)");
+    if (!t->envs.state) return rd::set_error(RD_EINVAL, "rdl_envs_reset: no envs attached (rdl_envs_attach)");
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdl_envs_reset");
-    const size_t n = (size_t)t->envs_n;
+    const size_t n = (size_t)t->envs.n;
     RD_HIP(hipMemsetAsync(t->env_q, 0, sizeof(float) * 2 * n * U, t->stream), "rdl_envs_reset: query state");
     RD_HIP(hipMemsetAsync(t->env_hist, 0, sizeof(float) * n * t->T * EH_REC, t->stream), "rdl_envs_reset: history");
-    hipLaunchKernelGGL(student_lstm_envs_reset_kernel, dim3((unsigned)((t->envs_n + 255) / 256)), dim3(256), 0, t->stream,
+    hipLaunchKernelGGL(student_lstm_envs_reset_kernel, dim3((unsigned)((t->envs.n + 255) / 256)), dim3(256), 0, t->stream,
                        envs_args(t));
     RD_HIP(hipGetLastError(), "student_lstm_envs_reset_kernel launch");
     return RD_OK;
 }
 
 int rdl_envs_attach(rdl_trainer* t, const rdl_envs_config* cfg) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_attach: null trainer");
-    if (!cfg) return rd::set_error(RD_EINVAL, "rdl_envs_attach: null config");
-    if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
-        return rd::set_error(RD_EINVAL, "rdl_envs_attach: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
-    if (cfg->env_base < 0) return rd::set_error(RD_EINVAL, "rdl_envs_attach: negative env_base");
-    if (cfg->grid < 0) return rd::set_error(RD_EINVAL, "rdl_envs_attach: negative grid");
+    if (int rc = rd::envs_attach_check("rdl_envs_attach", t, cfg)) return rc;
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdl_envs_attach");
-    if (t->env_state) {   // replace: launches that still read the old envs finish first
+    if (t->envs.state) {   // replace: launches that still read the old envs finish first
         RD_HIP(hipStreamSynchronize(t->stream), "rdl_envs_attach");
         free_envs(t);
     }
     const size_t n = (size_t)cfg->n_envs;
-    hipError_t e = hipMalloc((void**)&t->env_state, sizeof(float) * rd::kStateDim * n);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->env_aux, sizeof(float) * ENV_AUX * n);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->env_clock, sizeof(int32_t) * 2 * n);
+    hipError_t e = rd::envs_alloc(t->envs, *cfg, rd::kStateDim, ENV_AUX);
     if (e == hipSuccess) e = hipMalloc((void**)&t->env_q, sizeof(float) * 2 * n * U);
     if (e == hipSuccess) e = hipMalloc((void**)&t->env_hist, sizeof(float) * n * t->T * EH_REC);
     if (e != hipSuccess) {
         free_envs(t);
         return rd::hip_fail(e, "rdl_envs_attach: allocation");
     }
-    t->envs_n = cfg->n_envs;
-    t->envs_base = cfg->env_base;
-    t->envs_seed = cfg->seed;
-    t->envs_grid = cfg->grid;
     return rdl_envs_reset(t);
 }
 
@@ -1052,28 +1014,18 @@ int rdl_step_envs(rdl_trainer* t, int act_with, int steps, float* records, float
 
 int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode) {
     if (!t || !state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: null trainer or state");
-    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: no envs attached (rdl_envs_attach)");
+    if (!t->envs.state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: no envs attached (rdl_envs_attach)");
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdl_envs_get_state");
-    RD_HIP(hipMemcpyAsync(state, t->env_state, sizeof(float) * rd::kStateDim * t->envs_n, hipMemcpyDeviceToDevice,
-                          t->stream), "rdl_envs_get_state: copy");
-    int32_t c[2] = {0, 0};
-    RD_HIP(hipMemcpyAsync(&c[0], t->env_clock, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
-           "rdl_envs_get_state: clock");
-    RD_HIP(hipMemcpyAsync(&c[1], t->env_clock + t->envs_n, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream),
-           "rdl_envs_get_state: clock");
-    RD_HIP(hipStreamSynchronize(t->stream), "rdl_envs_get_state");
-    if (step) *step = c[0];
-    if (episode) *episode = c[1];
-    return RD_OK;
+    return rd::envs_get_state("rdl_envs_get_state", t->envs, rd::kStateDim, t->stream, state, step, episode);
 }
 
 int rdl_envs_get_query_state(rdl_trainer* t, float* state_out) {
     if (!t || !state_out) return rd::set_error(RD_EINVAL, "rdl_envs_get_query_state: null trainer or state_out");
-    if (!t->env_state) return rd::set_error(RD_EINVAL, "rdl_envs_get_query_state: no envs attached (rdl_envs_attach)");
+    if (!t->envs.state) return rd::set_error(RD_EINVAL, "rdl_envs_get_query_state: no envs attached (rdl_envs_attach)");
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdl_envs_get_query_state");
-    RD_HIP(hipMemcpyAsync(state_out, t->env_q, sizeof(float) * 2 * t->envs_n * U, hipMemcpyDeviceToDevice, t->stream),
+    RD_HIP(hipMemcpyAsync(state_out, t->env_q, sizeof(float) * 2 * t->envs.n * U, hipMemcpyDeviceToDevice, t->stream),
            "rdl_envs_get_query_state: copy");
     return RD_OK;
 }
