@@ -12,7 +12,10 @@ the f64 oracle (bf16 is what runs; the emulation alone gives 0.68-0.75); over al
 most 1 % of pdflat outside that tolerance against the emulation (stand-in: 0 of 18,228).  Gradient: the
 f32 test's bounds against the emulation (relative L2 < 5e-4, per element <= 1e-3 max|g| + 1e-6), and
 rel(got, emulation) <= 0.25 rel(emulation, oracle), both computed here (stand-in ratios 0.0001 ..
-0.028; an f32 gradient has ratio ~1 and fails by construction).
+0.028; an f32 gradient has ratio ~1 and fails by construction), and tests/student_parity.py's per-entry
+bound against the emulation, with its bf16 tolerances and the scale M on the emulation's rounded operands
+(asserted from 2,000 windows on, here (4, 2000); below, one rounding flip exceeds its cap, so only the exact
+zeros are asserted and the figure is printed: that module's "Tolerances").
 """
 import functools
 
@@ -23,6 +26,7 @@ import torch
 from oracle import lstm_np as ln
 from oracle import policy_np as pn
 from tests import lstm_bf16 as lb
+from tests import student_parity as sp
 from tests.test_student_lstm_envs_gpu import STEPS, _student, tr   # noqa: F401  (tr: the teacher's fixture)
 
 pytestmark = pytest.mark.gpu
@@ -40,13 +44,14 @@ def _t(x):
     return torch.from_numpy(np.ascontiguousarray(x))
 
 
-def _grad_check(g, want):
+def _grad_check(g, want, M, label, rows, bf16=True):
     """tests/test_student_lstm_gpu.py's gradient bounds."""
     g = np.asarray(g, np.float64)
     rel = lb.rel_l2(g, want)
     print(f"rel L2 {rel:.3e}  max err {np.abs(g - want).max():.3e}  max |g| {np.abs(want).max():.3e}")
     assert rel < 5e-4, rel
     assert np.abs(g - want).max() <= 1e-3 * np.abs(want).max() + 1e-6
+    sp.check_grad(g, dict(g64=want, M=M), label, rows, bf16)
     return rel
 
 
@@ -93,18 +98,20 @@ def test_forward_outputs_of_all_shapes_stay_inside_the_f32_tolerance_of_the_emul
 
 
 # ---------------------------------------------------------------- gradient
-def _gradient_case(T, B, loss, with_state=False, keep_prob=1.0, seed=0):
+def _gradient_case(T, B, loss, with_state=False, keep_prob=1.0, seed=0, **kw):
     ob, prev, t = lb.batch(T, B, 3 + B)
     st = lb.state(B, 2) if with_state else None
-    tr_ = _trainer(T, B, loss, keep_prob=keep_prob, seed=seed)
+    tr_ = _trainer(T, B, loss, keep_prob=keep_prob, seed=seed, **kw)
     p = tr_.params().cpu().numpy()
     g = tr_.rollout(_t(ob), _t(prev), _t(t), None if st is None else _t(st)).cpu().numpy()
     tr_.apply()
     m = tr_.metrics(1)[0]
     tr_.close()
-    ge, L, sq, _ = lb.step_gradient(p, ob, prev, t, loss, st, keep_prob=keep_prob, seed=seed)
+    ge, L, sq, fw = lb.step_gradient(p, ob, prev, t, loss, st, keep_prob=keep_prob, seed=seed)
     go, _, _, _ = lb.step_gradient(p, ob, prev, t, loss, st, keep_prob=keep_prob, seed=seed, rounded=False)
-    rel = _grad_check(g, ge)
+    M = sp.lstm_scale(p, fw, ln.loss_and_dout(fw["pdflat"], t, loss, T * B)[1], rounded=True)
+    what = " ".join(sorted(kw) + ["from a state"] * with_state + ["dropout"] * (keep_prob < 1))
+    rel = _grad_check(g, ge, M, f"lstm bf16 {loss} ({T},{B}) {what or 'default'}", B)
     cap = lb.rel_l2(ge, go)
     print(f"rel(got, emulation) {rel:.3e}  rel(emulation, oracle) {cap:.3e}  ratio {rel / cap:.4f}")
     assert rel <= 0.25 * cap, (rel, cap)
@@ -116,6 +123,16 @@ def _gradient_case(T, B, loss, with_state=False, keep_prob=1.0, seed=0):
 @pytest.mark.parametrize("T,B", [(10, 1), (10, 20), (10, 65), (4, 330), (4, 2000), (1, 7)])
 def test_gradient_and_metrics_match_the_emulation(loss, T, B):
     _gradient_case(T, B, loss)
+
+
+# The per-step shapes of tests/test_student_lstm_gpu.py's PATH_CASES (a bf16 handle takes no other path): the
+# weight gradient's 64-row chunks (bf_wg_chunk) end in 54, 10 and 18 rows, none a multiple of the MFMA's 32-row
+# k step; (10, 53): the fused head's last tile holds 5 windows
+@pytest.mark.parametrize("loss", ["mse", "kl"])
+@pytest.mark.parametrize("layer_head", [False, True])
+@pytest.mark.parametrize("T,B", [(10, 31), (10, 33), (10, 53)])
+def test_gradient_at_the_per_step_edges(loss, layer_head, T, B):
+    _gradient_case(T, B, loss, **({"layer_head": True} if layer_head else {}))
 
 
 def test_gradient_from_a_given_initial_state():
@@ -199,7 +216,9 @@ def test_sharded_windows_sum_to_the_full_batch():
     gf = full.rollout(_t(ob), _t(prev), _t(t)).clone()
     ga = a.rollout(_t(ob[:, :25]), _t(prev[:, :25]), _t(t[:, :25]), windows_global=B).clone()
     gb = b.rollout(_t(ob[:, 25:]), _t(prev[:, 25:]), _t(t[:, 25:]), windows_global=B).clone()
-    _grad_check((ga + gb).cpu().numpy(), gf.cpu().numpy().astype(np.float64))
+    M = sp.lstm_reference(lb.params(), ob, prev, t, "mse", rounded=True, keep_prob=0.8, seed=3)["M"]
+    _grad_check((ga + gb).cpu().numpy(), gf.cpu().numpy().astype(np.float64), M, "lstm bf16 sharded 25 + 35 vs 60", B,
+                bf16=False)   # two device gradients of the same arithmetic: the f32 bounds
     for x in (full, a, b):
         x.close()
 

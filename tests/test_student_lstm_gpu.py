@@ -2,8 +2,9 @@
 oracle/lstm_np.py (f64).
 
 Tolerances (f32 kernels through T recurrent steps vs the f64 oracle): pdflat and final
-state |err| <= 5e-5 + 1e-4 |ref|; gradient relative L2 error < 5e-4 and per element
-<= 1e-3 max|g| + 1e-6; Adam step within 1e-6 + 1e-3 |update| where |g| > 1e-4 max|g|
+state |err| <= 5e-5 + 1e-4 |ref|; gradient relative L2 error < 5e-4, per element
+<= 1e-3 max|g| + 1e-6, and tests/student_parity.py's per-entry bound (each entry against the sum
+over windows and steps of |the row's contribution|); Adam step within 1e-6 + 1e-3 |update| where |g| > 1e-4 max|g|
 (elsewhere Adam's ~lr sign(g) step is bounded by 2 lr).
 """
 import numpy as np
@@ -12,6 +13,7 @@ import torch
 
 from oracle import lstm_np as ln
 from oracle import policy_np as pn
+from tests import student_parity as sp
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -44,11 +46,14 @@ def _t(x):
     return torch.from_numpy(np.ascontiguousarray(x))
 
 
-def _grad_check(g, want):
+def _grad_check(g, want, M, label, rows):
+    """want: the oracle's gradient (or, sharded, the full batch's from the GPU); M: the per-entry
+    scale of the full batch (student_parity.lstm_scale)."""
     g = np.asarray(g, np.float64)
     rel = np.linalg.norm(g - want) / np.linalg.norm(want)
     assert rel < 5e-4, rel
     assert np.abs(g - want).max() <= 1e-3 * np.abs(want).max() + 1e-6
+    sp.check_grad(g, dict(g64=want, M=M), label, rows)
     return rel
 
 
@@ -76,10 +81,80 @@ def test_bptt_gradient_and_metrics_match_oracle(loss, T, B):
     g = tr.rollout(_t(ob), _t(prev), _t(t)).cpu().numpy()
     fw = ln.forward(p, ob, prev)
     L, d, sq = ln.loss_and_dout(fw["pdflat"], t, loss, T * B)
-    _grad_check(g, ln.backward(p, fw, d))
+    _grad_check(g, ln.backward(p, fw, d), sp.lstm_scale(p, fw, d), f"lstm f32 {loss} ({T},{B})", B)
     tr.apply()
     m = tr.metrics(1)[0]
     assert abs(m[0] - L) <= 2e-4 * abs(L) + 1e-6 and abs(m[1] - sq) <= 2e-4 * sq + 1e-6 and m[2] == T * B
+
+
+# The path each shape reaches (csrc/student_lstm.hip path_of; rd_gemm.h gemm_plan splits K only from K = T B
+# >= 512 rows on):
+#   B <= 32: the persistent forward and BPTT launches; past it, or with step_recurrence, the per-step launches,
+#     whose dWl is two GEMMs over all K = T B rows ([x]^T dz: 43 x 800, 13 tiles; [h]^T dz: 200 x 800, 52 tiles);
+#   (10, 53): K = 530, not a multiple of 16; the x part splits into 96-row chunks (5 and a last one of 50), the h
+#     part into 288 + 242; the fused head's last 16-row tile holds 5 windows;
+#   layer_head: the per-layer head GEMMs (K = B per step) for the one-launch head and its per-workgroup partials.
+PATH_CASES = [
+    (10, 31, {}),                               # persistent, 31 of 32 rows; head tiles 16 + 15
+    (10, 32, {}),                               # persistent, the last size it takes
+    (2, 17, {}),                                # persistent, two steps, head tiles 16 + 1
+    (10, 33, {}),                               # the first size past it: per step, K = 330 unsplit, head tiles 16 + 16 + 1
+    (10, 31, {"step_recurrence": True}),        # per step at a persistent size, K = 310 = 19 x 16 + 6
+    (10, 53, {"step_recurrence": True}),        # per step, split K with a shorter last chunk, ragged head tile
+]
+PATH_CASES += [(T, B, dict(kw, layer_head=True)) for T, B, kw in PATH_CASES]
+
+
+@pytest.mark.parametrize("loss", ["mse", "kl"])
+@pytest.mark.parametrize("T,B,kw", PATH_CASES)
+def test_gradient_on_every_path_at_its_edges(loss, T, B, kw):
+    tr = _trainer(T, B, loss, **kw)
+    assert tr.fused_head == (not kw.get("layer_head"))
+    ob, prev, t = _batch(T, B, 3 + B)
+    p = tr.params().cpu().numpy()
+    g = tr.rollout(_t(ob), _t(prev), _t(t)).cpu().numpy()
+    fw = ln.forward(p, ob, prev)
+    _, d, _ = ln.loss_and_dout(fw["pdflat"], t, loss, T * B)
+    flags = " ".join(sorted(kw)) or "default"
+    _grad_check(g, ln.backward(p, fw, d), sp.lstm_scale(p, fw, d), f"lstm f32 {loss} ({T},{B}) {flags}", B)
+    tr.close()
+
+
+@pytest.mark.parametrize("B,kw", [(32, {}), (33, {}), (16, {"layer_head": True})])
+def test_each_window_contribution_isolated(B, kw):
+    """T = 10, kl: 32 windows on the persistent path, 33 on the per-step path, 16 with the per-layer
+    head.  g(batch) - g(batch with window r replaced by a fixed window z) is c(x_r) - c(z) (a
+    window's contribution does not depend on the others), compared per entry with the oracle's for
+    every r under student_parity's isolation bound."""
+    T = 10
+    tr = _trainer(T, B, "kl", **kw)
+    ob, prev, t = _batch(T, B, 41 + B)
+    zo, zp, zt = sp.iso_lstm_z(T)
+    p = tr.params().cpu().numpy()
+
+    def grad_of(o, q, tg):
+        return tr.rollout(_t(o), _t(q), _t(tg)).cpu().numpy().astype(np.float64)
+
+    ref = sp.lstm_reference(p, ob, prev, t, "kl")
+    refz = sp.lstm_reference(p, zo[:, None], zp[:, None], zt[:, None], "kl", windows_global=B)
+    g_all = grad_of(ob, prev, t)
+    flags = " ".join(sorted(kw)) or "default"
+    sp.check_grad(g_all, ref, f"lstm f32 isolation kl ({T},{B}) {flags} batch", B)
+    lay = sp.lstm_layout(T)[0]
+    worst = (0.0, 0, 0)
+    for r in range(B):
+        oe, qe, te = ob.copy(), prev.copy(), t.copy()
+        oe[:, r], qe[:, r], te[:, r] = zo, zp, zt
+        d_gpu = g_all - grad_of(oe, qe, te)
+        Mx = sp.scale(ref["products"], p.size, [r])
+        d64 = sp.row_contribution(ref["products"], p.size, [r]) - refz["g64"]
+        bound = sp.isolation_bound(Mx, refz["M"], ref["M"], ref["M"] - Mx + refz["M"])
+        ratio, k = sp.isolation_ratio(d_gpu, d64, bound)
+        worst = max(worst, (ratio, r, k))
+        assert ratio <= 1.0, (r, sp.block_of(lay, k), ratio)
+    print(f"student_parity isolation lstm f32 kl ({T},{B}) {flags}: worst error / bound {worst[0]:.3f} "
+          f"(window {worst[1]}, {sp.block_of(lay, worst[2])})")
+    tr.close()
 
 
 def test_gradient_from_a_given_initial_state():
@@ -91,7 +166,7 @@ def test_gradient_from_a_given_initial_state():
     g = tr.rollout(_t(ob), _t(prev), _t(t), _t(st)).cpu().numpy()
     fw = ln.forward(p, ob, prev, st)
     _, d, _ = ln.loss_and_dout(fw["pdflat"], t, "kl", T * B)
-    _grad_check(g, ln.backward(p, fw, d))
+    _grad_check(g, ln.backward(p, fw, d), sp.lstm_scale(p, fw, d), f"lstm f32 kl ({T},{B}) from a state", B)
 
 
 def test_adam_steps_match_oracle():
@@ -126,7 +201,7 @@ def test_dropout_matches_oracle_mask():
         g = tr.rollout(_t(ob), _t(prev), _t(t)).cpu().numpy()
         fw = ln.forward(p, ln.dropout(ob, 0.5, 77, step), prev)
         _, d, _ = ln.loss_and_dout(fw["pdflat"], t, "mse", T * B)
-        _grad_check(g, ln.backward(p, fw, d))
+        _grad_check(g, ln.backward(p, fw, d), sp.lstm_scale(p, fw, d), f"lstm f32 dropout mse ({T},{B}) step {step}", B)
         tr.apply()
 
 
@@ -141,7 +216,9 @@ def test_sharded_windows_sum_to_the_full_batch():
     b = StudentLstmTrainer(StudentLstmConfig(max_windows=35, **cfg), device=DEV, params=_params(), row_base=25)
     ga = a.rollout(_t(ob[:, :25]), _t(prev[:, :25]), _t(t[:, :25]), windows_global=B).clone()
     gb = b.rollout(_t(ob[:, 25:]), _t(prev[:, 25:]), _t(t[:, 25:]), windows_global=B).clone()
-    _grad_check((ga + gb).cpu().numpy(), gf.cpu().numpy().astype(np.float64))
+    fw = ln.forward(_params(), ln.dropout(ob, 0.8, 3, 0), prev)
+    M = sp.lstm_scale(_params(), fw, ln.loss_and_dout(fw["pdflat"], t, "mse", T * B)[1])
+    _grad_check((ga + gb).cpu().numpy(), gf.cpu().numpy().astype(np.float64), M, "lstm f32 sharded 25 + 35 vs 60", B)
 
 
 def test_deterministic():
@@ -221,7 +298,7 @@ def test_carried_state_chain_matches_oracle():
         g = tr.rollout(_t(ob), _t(prev), _t(t), s_dev).cpu().numpy()
         fw = ln.forward(p, ob, prev, s_np)
         _, d, _ = ln.loss_and_dout(fw["pdflat"], t, "kl", T * B)
-        _grad_check(g, ln.backward(p, fw, d))
+        _grad_check(g, ln.backward(p, fw, d), sp.lstm_scale(p, fw, d), f"lstm f32 kl ({T},{B}) carried state, window {k}", B)
         tr.apply()
         s_dev = tr.final_state(B)
         s_np = np.stack(fw["state"]).astype(np.float32)
@@ -263,7 +340,7 @@ def test_checkpoint_round_trip(tmp_path, fmt):
     fw = ln.forward(p0, ob, prev)
     _, d, _ = ln.loss_and_dout(fw["pdflat"], t, "kl", T * B)
     g = b.rollout(_t(ob), _t(prev), _t(t)).cpu().numpy()
-    _grad_check(g, ln.backward(p0, fw, d))
+    _grad_check(g, ln.backward(p0, fw, d), sp.lstm_scale(p0, fw, d), f"lstm f32 kl ({T},{B}) restored from {fmt}", B)
     b.apply()
     m, v = m0, v0
     m = m + (g - m) * np.float32(0.1)
@@ -308,7 +385,9 @@ def test_persistent_recurrence_matches_per_step_launches(T, B, with_state):
     p = out["1"][4]
     fw = ln.forward(p, ob, prev, st)
     _, d, _ = ln.loss_and_dout(fw["pdflat"], t, "kl", T * B)
-    _grad_check(g1, ln.backward(p, fw, d))
+    M = sp.lstm_scale(p, fw, d)
+    _grad_check(g1, ln.backward(p, fw, d), M, f"lstm f32 kl ({T},{B}) persistent, state {with_state}", B)
+    _grad_check(g0, ln.backward(p, fw, d), M, f"lstm f32 kl ({T},{B}) per step, state {with_state}", B)
 
 
 @pytest.mark.parametrize("T,B", [(10, 20), (3, 130), (1, 5), (10, 4100), (4, 16384), (10, 16384)])

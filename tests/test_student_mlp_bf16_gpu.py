@@ -20,7 +20,11 @@ of all shapes together (measured 16 of 2,776 = 0.58 %; 0.88 % at n = 4,099).  Pe
 (<= 260 outputs) a 1 % cap on the one shape would allow no flip at all, and grid=2 n=65 has one such
 row (3 of 260 outputs).
 Gradient: relative L2 < 2e-4 against the emulation (the f32 test's bound; measured 4e-8 without a
-flip, up to 4.8e-5 with), > 1e-3 against the f64 oracle's gradient (measured 2.4e-3 .. 4.4e-3).
+flip, up to 4.8e-5 with), > 1e-3 against the f64 oracle's gradient (measured 2.4e-3 .. 4.4e-3), and
+tests/student_parity.py's per-entry bound against the emulation, with its bf16 tolerances and the scale
+M on the emulation's rounded operands (asserted from 2,000 rows on, which no shape here reaches; below,
+one rounding flip exceeds its cap, so only the exact zeros are asserted and the figure is printed: that
+module's "Tolerances").
 The bitwise contracts (evaluate, act_envs, step_envs against the stepwise loop)
 are those of tests/test_student_mlp_evaluate_gpu.py and tests/test_student_mlp_envs_gpu.py, whose
 helpers are imported unchanged.
@@ -34,6 +38,7 @@ import torch
 from oracle import policy_np as pn
 from oracle import refnet_np as rn
 from tests import refnet_bf16 as rb
+from tests import student_parity as sp
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -96,21 +101,23 @@ def test_forward_share_outside_the_f32_tolerance():
     assert rb.outside(got, want) <= 0.01
 
 
-def _grad_check(g, want):   # tests/test_student_mlp_gpu.py's bounds
+def _grad_check(g, want, M, label, rows, bf16=True):   # tests/test_student_mlp_gpu.py's bounds
     rel = rb.rel_l2(g, want)
     assert rel < 2e-4, rel
     assert np.abs(np.asarray(g, np.float64) - want).max() <= 1e-4 * np.abs(want).max() + 1e-6
+    sp.check_grad(g, dict(g64=want, M=M), label, rows, bf16)
     return rel
 
 
-def _check_step(tr, x, t, loss, n, **drop):
+def _check_step(tr, x, t, loss, n, label="", **drop):
     p = tr.params().cpu().numpy()
     g = tr.rollout(torch.from_numpy(x), torch.from_numpy(t)).cpu().numpy()
     want, lval, sq = rb.step_gradient(p, x, t, loss, **drop)
     oracle, _, _ = rb.step_gradient(p, x, t, loss, rounded=(), **drop)
     rel = rb.rel_l2(g, want)
     print("gradient %s n=%d: rel L2 %.3e vs emulation, %.3e vs oracle" % (loss, n, rel, rb.rel_l2(g, oracle)))
-    _grad_check(g, want)
+    M = sp.mlp_reference(p, x, t, loss, rounded=rb.BF_LAYERS, **drop)["M"]
+    _grad_check(g, want, M, f"mlp bf16 {loss} n={n}{label}", n)
     assert rb.rel_l2(g, oracle) > 1e-3
     tr.apply()
     m = tr.metrics(1)[0]
@@ -122,14 +129,27 @@ def _check_step(tr, x, t, loss, n, **drop):
 def test_gradient_and_metrics_match_the_emulation(loss, grid, n):
     tr = _trainer(loss, grid=grid)
     x, t = rb.batch(n, 7 + n)
-    _check_step(tr, x, t, loss, n)
+    _check_step(tr, x, t, loss, n, f" grid={grid}")
+    tr.close()
+
+
+# tests/test_student_mlp_gpu.py's EDGE_SHAPES, with the paths they reach (the BF = true instances of the
+# same two kernels)
+@pytest.mark.parametrize("loss", ["mse", "kl"])
+@pytest.mark.parametrize("grid", [0, 2])
+@pytest.mark.parametrize("n", [15, 16, 17, 63, 64, 65, 129])
+def test_gradient_at_the_block_edges(loss, grid, n):
+    tr = _trainer(loss, grid=grid)
+    # at most 20 rows: a batch without a forward operand on a bf16 tie (student_parity.mlp_bf16_seed)
+    x, t = rb.batch(n, sp.mlp_bf16_seed(n, 7 + n) if n <= sp.TIE_MAX_ROWS else 7 + n)
+    _check_step(tr, x, t, loss, n, f" grid={grid}")
     tr.close()
 
 
 def test_dropout_matches_the_emulations_mask():
     tr = _trainer("kl", keep_prob=0.5, seed=99)
     x, t = rb.batch(200, 5)
-    _check_step(tr, x, t, "kl", 200, keep_prob=0.5, seed=99, step=0)
+    _check_step(tr, x, t, "kl", 200, " dropout", keep_prob=0.5, seed=99, step=0)
     tr.close()
 
 
@@ -179,7 +199,9 @@ def test_sharded_rows_sum_to_the_full_batch():
     b = StudentMlpTrainer(cfg, device=DEV, params=rb.params(), row_base=600)
     ga = a.rollout(torch.from_numpy(x[:600]), torch.from_numpy(t[:600]), n_global=1000).clone()
     gb = b.rollout(torch.from_numpy(x[600:]), torch.from_numpy(t[600:]), n_global=1000).clone()
-    _grad_check((ga + gb).cpu().numpy(), full.cpu().numpy().astype(np.float64))
+    M = sp.mlp_reference(rb.params(), x, t, "mse", rounded=rb.BF_LAYERS, keep_prob=0.7, seed=5)["M"]
+    _grad_check((ga + gb).cpu().numpy(), full.cpu().numpy().astype(np.float64), M, "mlp bf16 sharded 600 + 400 vs 1000", 1000,
+                bf16=False)   # two device gradients of the same arithmetic: the f32 bounds
 
 
 # -- the bitwise contracts, in bf16 ---------------------------------------------------------------
