@@ -104,6 +104,9 @@ int rd_replay_push_episodes(rd_replay* h, const float* records, int64_t episodes
  * NULL x, t_pdflat or reward. */
 int rd_replay_push_rows(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat,
                         const float* reward, const float* carry, int64_t steps, int64_t n_envs, float stepped_with);
+/* (The form with a stepped_with per row, rd_replay_push_rows_flags, is declared beside the call that
+ * fills its flags, rdm_envs_bind_stepped_with in reacher_student_mlp.h: this header's list of names is
+ * as it was.) */
 
 typedef struct {
     int32_t steps;        /* T, 1 .. 50 (rd_replay_sample_rows ignores it)          */

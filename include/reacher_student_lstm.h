@@ -291,6 +291,30 @@ int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* epi
 /* the envs' query state [2][n_envs][200] = (c, h) (device), asynchronous */
 int rdl_envs_get_query_state(rdl_trainer* t, float* state_out);
 
+/* DAgger's beta-mixture pi_i = beta pi* + (1 - beta) pi^_i in the RDL_ACT_STUDENT calls above: the
+ * handle has a teacher share beta in [0, 1] and a 64-bit coin seed; the default beta = 0 leaves every
+ * call exactly as described above (the same launch of the same kernel).  RDL_ACT_TEACHER ignores
+ * beta.  In a mixed call an env step is the student step -- T_s and S_s both computed, S_s in the
+ * record, (c, h) read and replaced, the ring kept and the windows written -- and only the action
+ * handed to env.step differs, by a coin per env and step:
+ *   e    = env_base + i
+ *   w    = word 0 of Philox4x32-10(ctr = {e lo, e hi, episode, 0x80000000 | s}, key = {coin_seed lo, hi})
+ *   coin = (w >> 8) 2^-24 < beta             (the teacher acts)
+ *   mean = coin ? T_s[0..1] : S_s[0..1];   the record's stepped_with = coin ? 0 : 1
+ * s and episode are the env's device clock, so the coin is a function of (coin seed, env, episode,
+ * step) alone: it does not depend on the grid or the split of the steps over calls, and a captured
+ * call replays the NEXT steps' coins.  Counter word 3 has its top bit set: the stream is disjoint from
+ * the reset draws' (word 3 = 0, 1) even under equal seeds.  beta and the coin seed are kernel
+ * arguments: a captured call keeps the values it was captured with, whatever is set later.
+ * Training is unchanged: rdl_rollout_envs / rdl_step_envs train on all the in-episode windows, every
+ * visited state carrying its teacher label whoever stepped it.  SINGLE GPU ONLY, as above.
+ * rdl_envs_set_teacher_share is host-only, like rdl_set_query_dtype (no device call, no allocation,
+ * no synchronisation); the next call takes the new setting; it may precede rdl_envs_attach and
+ * survives attach and reset.  RD_EINVAL, naming the function and the field, before the handle is
+ * read: NULL trainer; beta NaN, < 0 or > 1.  rdl_envs_teacher_share returns beta, -1 for NULL. */
+int rdl_envs_set_teacher_share(rdl_trainer* t, float beta, uint64_t coin_seed);
+float rdl_envs_teacher_share(const rdl_trainer* t);
+
 #ifdef __cplusplus
 }
 #endif

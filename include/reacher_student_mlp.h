@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "reacher.h"
+#include "reacher_replay.h"   /* rd_replay: rd_replay_push_rows_flags, below */
 
 #ifdef __cplusplus
 extern "C" {
@@ -200,6 +201,41 @@ int rdm_rollout_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t
 int rdm_step_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward);
 /* state [8][n_envs] SoA as rd_get_state (device); env 0's clock; host-synchronising */
 int rdm_envs_get_state(rdm_trainer* t, float* state, int32_t* step, int32_t* episode);
+
+/* DAgger's beta-mixture pi_i = beta pi* + (1 - beta) pi^_i in the RDM_ACT_STUDENT calls above: the
+ * handle has a teacher share beta in [0, 1] and a 64-bit coin seed; the default beta = 0 leaves every
+ * call exactly as described above (the same launch of the same kernel).  RDM_ACT_TEACHER ignores
+ * beta.  In a mixed call an env step is the student step -- T_s and S_s both computed, S_s written to
+ * s_pdflat -- and only the action handed to env.step differs, by a coin per env and step:
+ *   e    = env_base + i
+ *   w    = word 0 of Philox4x32-10(ctr = {e lo, e hi, episode, 0x80000000 | s}, key = {coin_seed lo, hi})
+ *   coin = (w >> 8) 2^-24 < beta             (the teacher acts)
+ *   mean = coin ? T_s[0..1] : S_s[0..1];   stepped_with = coin ? 0 : 1
+ * s and episode are the env's device clock, so the coin is a function of (coin seed, env, episode,
+ * step) alone: it does not depend on the grid, the block size or the split of the steps over calls,
+ * and a captured call replays the NEXT steps' coins.  Counter word 3 has its top bit set: the stream
+ * is disjoint from the reset draws' (word 3 = 0, 1) even under equal seeds.  beta and the coin seed
+ * are kernel arguments: a captured call keeps the values it was captured with, whatever is set later.
+ * Training is unchanged: rdm_rollout_envs / rdm_step_envs train on all K n_envs rows, every visited
+ * state carrying its teacher label whoever stepped it.  Multi-GPU stays out of scope, as above.
+ * rdm_envs_set_teacher_share is host-only (no device call, no allocation, no synchronisation); the
+ * next call takes the new setting; it may precede rdm_envs_attach and survives attach and reset.
+ * RD_EINVAL, naming the function and the field, before the handle is read: NULL trainer; beta NaN,
+ * < 0 or > 1.  rdm_envs_teacher_share returns beta, -1 for a NULL trainer. */
+int rdm_envs_set_teacher_share(rdm_trainer* t, float beta, uint64_t coin_seed);
+float rdm_envs_teacher_share(const rdm_trainer* t);
+/* Where the per-row stepped_with goes: buf = a caller-owned device buffer [K][n_envs] of `rows`
+ * floats, step-major as reward.  Every later RDM_ACT_STUDENT call fills its steps x n_envs rows with
+ * 1 (the student stepped) or 0 (the teacher's coin fell; all 1 at beta = 0), an RDM_ACT_TEACHER call
+ * with 0.  buf = NULL unbinds.  Host-only.  While a buffer is bound a call with steps x n_envs > rows
+ * is RD_EINVAL naming `rows`; so are a NULL trainer and rows < 1 with a buffer here. */
+int rdm_envs_bind_stepped_with(rdm_trainer* t, float* buf, int64_t rows);
+/* The replay ring's push for that buffer: rd_replay_push_rows (reacher_replay.h) with a stepped_with
+ * per row, stepped_with_rows [K][n] (required), step-major as reward, in place of the scalar.  The same
+ * copies, counter bump and argument checks; also RD_EINVAL for NULL stepped_with_rows. */
+int rd_replay_push_rows_flags(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat,
+                              const float* reward, const float* carry, int64_t steps, int64_t n_envs,
+                              const float* stepped_with_rows);
 
 #ifdef __cplusplus
 }

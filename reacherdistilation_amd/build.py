@@ -42,7 +42,8 @@ LDFLAGS = ["-shared", f"--offload-arch={ARCH}", "-ldl"]
 # reference student's kernel and reduce+Adam, the LSTM's BPTT, head and reduce kernels); every
 # product source is now scanned for it (tests/test_product_hygiene.py).
 NO_SLP = ["-fno-slp-vectorize"]
-SRC_FLAGS = {"distill.hip": NO_SLP, "ppo.hip": NO_SLP, "student_mlp.hip": NO_SLP, "student_lstm.hip": NO_SLP}
+SRC_FLAGS = {"distill.hip": NO_SLP, "ppo.hip": NO_SLP, "student_mlp.hip": NO_SLP, "student_mlp_mix.hip": NO_SLP,
+             "student_lstm.hip": NO_SLP}
 
 
 def src_flags(path):

@@ -292,6 +292,18 @@ __device__ __forceinline__ void philox_draw(uint64_t seed, uint64_t env_id, uint
     d[5] = __fmaf_rn(0.4f, u01(p[1]), -0.2f);
 }
 
+// DAgger's beta-mixture in the students' persistent envs (rdm_ / rdl_envs_set_teacher_share): the
+// teacher steps env `env_id` at step `step` of its episode iff u01(word 0 of Philox(ctr = env_id lo,
+// env_id hi, episode, 0x80000000 | step; key = coin_seed)) < beta.  Counter word 3 has its top bit
+// set: the reset draws above use 0 and 1, so the two streams are disjoint even under one seed.
+__device__ __forceinline__ bool teacher_coin(uint64_t coin_seed, uint64_t env_id, int32_t episode, int32_t step,
+                                             float beta) {
+    uint32_t o[4];
+    philox((uint32_t)env_id, (uint32_t)(env_id >> 32), (uint32_t)episode, 0x80000000u | (uint32_t)step,
+           (uint32_t)coin_seed, (uint32_t)(coin_seed >> 32), o);
+    return u01(o[0]) < beta;
+}
+
 // ------------------------------------------------------------------ envs a handle keeps on the device
 // (persistent envs: state [8][n], AUX rows of carried values [AUX][n], clock [2][n] = step of the
 // episode, episode.  student_lstm_envs.h calls these; student_mlp_envs.h has the same two bodies

@@ -76,13 +76,15 @@ __global__ __launch_bounds__(kBlock) void replay_push_episodes_kernel(float* __r
 }
 
 // rdm_envs_act's outputs, step-major; the record's fields are assembled per element
+// (with_rows: the per-row stepped_with [K][n] of rd_replay_push_rows_flags, else the scalar)
 __global__ __launch_bounds__(kBlock) void replay_push_rows_kernel(float* __restrict__ ring, const Header* hdr,
                                                                  const float* __restrict__ x,
                                                                  const float* __restrict__ t_pdflat,
                                                                  const float* __restrict__ s_pdflat,
                                                                  const float* __restrict__ reward,
                                                                  const float* __restrict__ carry, int64_t episodes,
-                                                                 int64_t n, int64_t capacity, float stepped_with) {
+                                                                 int64_t n, int64_t capacity, float stepped_with,
+                                                                 const float* __restrict__ with_rows) {
     const int64_t pushed = hdr->pushed;
     const int64_t total = episodes * (kSteps * kRec);
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void replay_push_rows_kernel(float* __restr
         else if (f == F_REW) v = k > 0 ? reward[row - n] : (carry ? carry[i] : 0.0f);
         else if (f < F_S) v = t_pdflat[row * kPd + (f - F_T)];
         else if (f < F_WITH) v = s_pdflat ? s_pdflat[row * kPd + (f - F_S)] : 0.0f;
-        else v = stepped_with;
+        else v = with_rows ? with_rows[row] : stepped_with;
         ring[ring_index(pushed, capacity, q, rem)] = v;
     }
 }
@@ -335,20 +337,37 @@ int rd_replay_push_episodes(rd_replay* h, const float* records, int64_t episodes
     return bump("rd_replay_push_episodes: bump launch", h, episodes, 0);
 }
 
+// rd_replay_push_rows and rd_replay_push_rows_flags, `fn` naming the caller; flags: the latter's
+// per-row stepped_with (required there)
+static int push_rows(const char* fn, rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat,
+                     const float* reward, const float* carry, int64_t steps, int64_t n_envs, float stepped_with,
+                     const float* with_rows, bool flags) {
+    if (!h) return rd::set_error(RD_EINVAL, "%s: null handle", fn);
+    if (!x) return rd::set_error(RD_EINVAL, "%s: null x", fn);
+    if (!t_pdflat) return rd::set_error(RD_EINVAL, "%s: null t_pdflat", fn);
+    if (!reward) return rd::set_error(RD_EINVAL, "%s: null reward", fn);
+    if (flags && !with_rows) return rd::set_error(RD_EINVAL, "%s: null stepped_with_rows", fn);
+    int64_t E = 0;
+    if (int rc = check_steps(fn, h, steps, n_envs, &E)) return rc;
+    rd::DeviceGuard g(h->device);
+    RD_HIP(g.err, fn);
+    hipLaunchKernelGGL(replay_push_rows_kernel, dim3(grid_for(E * kSteps * kRec)), dim3(kBlock), 0, h->stream, h->ring,
+                       h->hdr, x, t_pdflat, s_pdflat, reward, carry, E, n_envs, h->capacity, stepped_with, with_rows);
+    RD_HIP(hipGetLastError(), fn);
+    return bump(fn, h, E, 0);
+}
+
 int rd_replay_push_rows(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat, const float* reward,
                         const float* carry, int64_t steps, int64_t n_envs, float stepped_with) {
-    if (!h) return rd::set_error(RD_EINVAL, "rd_replay_push_rows: null handle");
-    if (!x) return rd::set_error(RD_EINVAL, "rd_replay_push_rows: null x");
-    if (!t_pdflat) return rd::set_error(RD_EINVAL, "rd_replay_push_rows: null t_pdflat");
-    if (!reward) return rd::set_error(RD_EINVAL, "rd_replay_push_rows: null reward");
-    int64_t E = 0;
-    if (int rc = check_steps("rd_replay_push_rows", h, steps, n_envs, &E)) return rc;
-    rd::DeviceGuard g(h->device);
-    RD_HIP(g.err, "rd_replay_push_rows: hipSetDevice");
-    hipLaunchKernelGGL(replay_push_rows_kernel, dim3(grid_for(E * kSteps * kRec)), dim3(kBlock), 0, h->stream, h->ring,
-                       h->hdr, x, t_pdflat, s_pdflat, reward, carry, E, n_envs, h->capacity, stepped_with);
-    RD_HIP(hipGetLastError(), "rd_replay_push_rows: launch");
-    return bump("rd_replay_push_rows: bump launch", h, E, 0);
+    return push_rows("rd_replay_push_rows", h, x, t_pdflat, s_pdflat, reward, carry, steps, n_envs, stepped_with, nullptr,
+                     false);
+}
+
+int rd_replay_push_rows_flags(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat,
+                              const float* reward, const float* carry, int64_t steps, int64_t n_envs,
+                              const float* stepped_with_rows) {
+    return push_rows("rd_replay_push_rows_flags", h, x, t_pdflat, s_pdflat, reward, carry, steps, n_envs, 0.0f,
+                     stepped_with_rows, true);
 }
 
 // the checks both samples share; those that need no handle come first

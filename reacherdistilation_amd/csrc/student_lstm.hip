@@ -110,6 +110,10 @@ struct rdl_trainer {
     float* wpart = nullptr;
     // the closed-loop query's arithmetic (rdl_set_query_dtype): RDL_DTYPE_BF16 reads wimg's forward image
     int qdtype = RDL_DTYPE_F32;
+    // DAgger's mixture in RDL_ACT_STUDENT calls (rdl_envs_set_teacher_share): host-side settings of the
+    // handle, not of its envs -- attach and reset leave them
+    float beta = 0.0f;         // the teacher's share of the env steps
+    uint64_t coin_seed = 0;
 };
 
 namespace {
@@ -628,6 +632,19 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
     auto* kern = !stu ? student_lstm_envs_kernel<false, false>
                  : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
+    // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0);
+    // otherwise the launch above, with the arguments it always had
+    if (stu && t->beta > 0.0f) {
+        LsEnvsMixArgs m{};
+        static_cast<LsEnvsArgs&>(m) = a;
+        m.beta = t->beta;
+        m.coin_seed = t->coin_seed;
+        auto* mixed = bf16_query(t) ? student_lstm_envs_kernel<true, true, true, LsEnvsMixArgs>
+                                    : student_lstm_envs_kernel<true, false, true, LsEnvsMixArgs>;
+        hipLaunchKernelGGL(mixed, grid, block, 0, t->stream, m);
+        RD_HIP(hipGetLastError(), "student_lstm_envs_kernel (mixed) launch");
+        return RD_OK;
+    }
     hipLaunchKernelGGL(kern, grid, block, 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_lstm_envs_kernel launch");
     return RD_OK;
@@ -1011,6 +1028,17 @@ int rdl_step_envs(rdl_trainer* t, int act_with, int steps, float* records, float
                   float* t_w) {
     return envs_train("rdl_step_envs", t, act_with, steps, records, reward, ob_w, prev_w, t_w, 1);
 }
+
+int rdl_envs_set_teacher_share(rdl_trainer* t, float beta, uint64_t coin_seed) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_teacher_share: null trainer");
+    if (!(beta >= 0.0f && beta <= 1.0f))   // NaN too
+        return rd::set_error(RD_EINVAL, "rdl_envs_set_teacher_share: beta %g outside 0 .. 1", (double)beta);
+    t->beta = beta;
+    t->coin_seed = coin_seed;
+    return RD_OK;
+}
+
+float rdl_envs_teacher_share(const rdl_trainer* t) { return t ? t->beta : -1.0f; }
 
 int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode) {
     if (!t || !state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: null trainer or state");

@@ -57,6 +57,13 @@ struct LsEnvsArgs {
     int steps, T;            // K
 };
 
+// the mixed instances' (rdl_envs_set_teacher_share).  A struct of its own: a longer LsEnvsArgs moves
+// the kernels' implicit arguments and hipcc then lays the other instances out anew
+struct LsEnvsMixArgs : LsEnvsArgs {
+    float beta;              // the teacher's share of the env steps
+    uint64_t coin_seed;      // the coins' Philox key
+};
+
 // episode 0 of every env; clock and aux to 0 (rd_reset's arithmetic); q and hist are memset by the host
 __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -65,8 +72,14 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
 
 // BF16Q: the student's positions run on the bf16 cell (student_lstm_query_bf16.h; a.img is then the
 // handle's WF image)
-template <bool STUDENT_ACTS, bool BF16Q>
-__global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArgs a) {
+// MIXED (with STUDENT_ACTS; DAgger's beta-mixture): the student instance's step, every piece and
+// barrier of it -- (c, h) read and replaced, the ring kept, the windows written -- and per env step a
+// coin in the env's lane (rd::teacher_coin: a function of (coin seed, env, episode, step) alone, so
+// known before the step and drawn before its first barrier) that hands the teacher's T_s[0..1] to
+// env_step instead of S_s[0..1]; the record's stepped_with is 1 - coin.
+template <bool STUDENT_ACTS, bool BF16Q, bool MIXED = false, class ARGS = LsEnvsArgs>
+__global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
+    static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
     const LsThread q = ls_prologue<STUDENT_ACTS>(a.tnet, a.P, a.img, a.T);
     const int tid = q.tid, lane = q.lane, T = q.T;
     const bool phys = q.wave == 0 && lane < EV_ROWS;   // the env of this lane
@@ -111,10 +124,14 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArg
         for (int k = 0; k < a.steps; ++k) {
             const int slot = s % T;
             float* rec = valid ? a.records + ((int64_t)k * n + env) * EV_REC : nullptr;
+            bool coin = false;   // MIXED: the teacher steps this env now
             if (phys) {   // record s, and its raw prev = T_{s-1} (zero at s = 0) into the ring
+                if constexpr (MIXED)
+                    coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) lds::Xr[slot][lane][EH_PREV + c] = s ? lds::TO[(s - 1) & 1][lane][c] : 0.0f;
-                ls_record_head(lane, slot, st, rec, carry, STUDENT_ACTS ? 1.0f : 0.0f);
+                if constexpr (MIXED) ls_record_head(lane, slot, st, rec, carry, coin ? 0.0f : 1.0f);
+                else ls_record_head(lane, slot, st, rec, carry, STUDENT_ACTS ? 1.0f : 0.0f);
             }
             // prev . Wp + bp of record s
             if (STUDENT_ACTS) lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
@@ -148,7 +165,8 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(LsEnvsArg
             if (phys) {
                 float sp[4];
                 ls_record_tail<STUDENT_ACTS>(lane, s, rec, tp, sp);
-                carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
+                if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
+                else carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
                 if (valid && a.reward) a.reward[(int64_t)k * n + env] = carry;
             }
             rd::env_time_limit(st, s, episode, a.seed, (uint64_t)(a.env_base + env), phys);   // resets inside its last step

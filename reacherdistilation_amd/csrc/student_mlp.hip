@@ -26,7 +26,8 @@
 // the kernels stand in the object -- the closed-loop evaluation over whole episodes (rdm_evaluate)
 // in student_mlp_eval.h, the persistent envs of the batched on-policy step (rdm_step_envs) in
 // student_mlp_envs.h, their common step in student_mlp_query.h.  This file keeps rdm_trainer, the
-// choice of the row block, one launch function per kernel family, and the C ABI.
+// choice of the row block, one launch function per kernel family, and the C ABI.  (The envs kernel's
+// mixed instances, DAgger's beta-mixture, are compiled in student_mlp_mix.hip: student_mlp_mix.h.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -38,6 +39,7 @@
 #include "rd_device.h"
 #include "rd_host.h"
 #include "rd_physics.h"
+#include "student_mlp_mix.h"
 
 namespace {
 
@@ -83,6 +85,12 @@ struct rdm_trainer {
     float* tnet = nullptr;      // rdm_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
     bool has_teacher = false;
     rd::EnvBufs envs;           // the persistent envs (rdm_envs_attach): state [8][n], aux [ENV_AUX][n], clock
+    // DAgger's mixture in RDM_ACT_STUDENT calls (rdm_envs_set_teacher_share, rdm_envs_bind_stepped_with):
+    // host-side settings of the handle, not of its envs -- attach and reset leave them
+    float beta = 0.0f;          // the teacher's share of the env steps
+    uint64_t coin_seed = 0;
+    float* flags = nullptr;     // the caller's stepped_with buffer [flag_rows], or null
+    int64_t flag_rows = 0;
 };
 
 namespace {
@@ -216,6 +224,10 @@ int envs_check(const char* fn, const rdm_trainer* t, int act_with, int steps, co
     if (t->envs.n > ((int64_t)1 << 31) / steps)
         return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs.n);
     if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdm_set_teacher)", fn);
+    if (t->flags && (int64_t)steps * t->envs.n > t->flag_rows)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the stepped_with buffer "
+                                        "(rdm_envs_bind_stepped_with)", fn, steps, (long long)t->envs.n,
+                             (long long)t->flag_rows);
     return RD_OK;
 }
 
@@ -233,6 +245,16 @@ int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdfl
     auto* kern = stu && t->bf ? (b.small ? student_mlp_envs_kernel<16, true, true> : student_mlp_envs_kernel<64, true, true>)
                  : b.small    ? (stu ? student_mlp_envs_kernel<16, true, false> : student_mlp_envs_kernel<16, false, false>)
                               : (stu ? student_mlp_envs_kernel<64, true, false> : student_mlp_envs_kernel<64, false, false>);
+    // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0) or a
+    // stepped_with buffer wants its flags; otherwise the launch above, with the arguments it always had
+    if (stu && (t->beta > 0.0f || t->flags)) {
+        const rd::MlpEnvsMixLaunch l{&a, t->beta, t->coin_seed, t->flags, t->bf, b.small, b.grid, b.threads, t->stream};
+        RD_HIP(rd::launch_mlp_envs_mixed(l), "student_mlp_envs_kernel (mixed) launch");   // student_mlp_mix.hip
+        return RD_OK;
+    }
+    if (t->flags)   // the teacher stepped every row
+        RD_HIP(hipMemsetAsync(t->flags, 0, sizeof(float) * (size_t)steps * (size_t)a.n, t->stream),
+               "student_mlp_envs_kernel: stepped_with");
     hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_envs_kernel launch");
     return RD_OK;
@@ -494,6 +516,25 @@ int rdm_rollout_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t
 
 int rdm_step_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdflat, float* s_pdflat, float* reward) {
     return envs_train("rdm_step_envs", t, act_with, steps, x, t_pdflat, s_pdflat, reward, 1);
+}
+
+int rdm_envs_set_teacher_share(rdm_trainer* t, float beta, uint64_t coin_seed) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_teacher_share: null trainer");
+    if (!(beta >= 0.0f && beta <= 1.0f))   // NaN too
+        return rd::set_error(RD_EINVAL, "rdm_envs_set_teacher_share: beta %g outside 0 .. 1", (double)beta);
+    t->beta = beta;
+    t->coin_seed = coin_seed;
+    return RD_OK;
+}
+
+float rdm_envs_teacher_share(const rdm_trainer* t) { return t ? t->beta : -1.0f; }
+
+int rdm_envs_bind_stepped_with(rdm_trainer* t, float* buf, int64_t rows) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_bind_stepped_with: null trainer");
+    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_stepped_with: rows %lld < 1", (long long)rows);
+    t->flags = buf;
+    t->flag_rows = buf ? rows : 0;
+    return RD_OK;
 }
 
 int rdm_envs_get_state(rdm_trainer* t, float* state, int32_t* step, int32_t* episode) {

@@ -38,6 +38,14 @@ struct SmEnvsArgs {
     int steps;               // K
 };
 
+// the mixed instances' (rdm_envs_set_teacher_share).  A struct of its own: a longer SmEnvsArgs moves
+// the kernels' implicit arguments and hipcc then lays the other instances out anew
+struct SmEnvsMixArgs : SmEnvsArgs {
+    float beta;              // the teacher's share of the env steps
+    uint64_t coin_seed;      // the coins' Philox key
+    float* stepped_with;     // [K][n] or null: 1 where the student's action stepped the env, else 0
+};
+
 // episode 0 of every env; clocks, carried reward and previous fields to 0 (rd_reset's arithmetic)
 __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -48,12 +56,22 @@ __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs 
 // next weights into the bias quad its four row blocks' first MFMAs share as SrcC (hazards.py LDSRC).
 // Fencing every layer scans clean too and costs 2-3 % of the launch
 // (profiles/student_mlp_envs_fence_ab.txt)
-template <int ROWS, bool STUDENT_ACTS, bool BF>
-__global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(SmEnvsArgs a) {
+// MIXED (with STUDENT_ACTS; DAgger's beta-mixture): the student instance's step, every layer, barrier
+// and fence of it, and per env step a coin in the env's lane -- rd::teacher_coin, a function of
+// (coin seed, env, episode, step) alone, drawn before the step's first barrier so that it runs beside
+// the layers -- that hands the teacher's T_s[0..1] to env_step instead of S_s[0..1].  x, t_pdflat and
+// s_pdflat are written as the student instance writes them; the coin goes to stepped_with.
+template <int ROWS, bool STUDENT_ACTS, bool BF, bool MIXED = false, class ARGS = SmEnvsArgs>
+__global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(ARGS a) {
+    // MIXED: the teacher steps this lane's env now.  The kernel's first local: declared inside the step
+    // loop it moves hipcc's layout of the six instances that never read it
+    // (profiles/envs_teacher_share_isa.txt)
+    bool coin = false;
     __shared__ __attribute__((aligned(16))) float lds[ELay<ROWS>::LDS_FLOATS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
     tch::load_net(lds + ELay<ROWS>::O_NET, a.tnet, false, ELay<ROWS>::THREADS);   // published by the first step's barriers
     const bool phys = wave == 0 && lane < ROWS;   // the env of this lane
+    static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
     const int64_t n = a.n, nblk = (n + ROWS - 1) / ROWS;
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int64_t row0 = blk * ROWS;
@@ -76,6 +94,8 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(S
         for (int k = 0; k < a.steps; ++k) {
             const int64_t out = (int64_t)k * n + env;   // row of this env's k-th step of the call
             if (phys) {
+                if constexpr (MIXED)
+                    coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
                 float row[RDM_IN];
                 qs_row<ROWS, STUDENT_ACTS>(lds, lane, st, s, tp, prev_field, row);
                 if (valid) {
@@ -90,7 +110,8 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(S
             if (phys) {
                 float sp[RDM_OUT];
                 qs_outputs<ROWS, STUDENT_ACTS>(lds, lane, sp, tp);
-                carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
+                if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
+                else carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
                 if (valid) {
                     *reinterpret_cast<f32x4*>(a.t_pdflat + out * RDM_OUT) = f32x4{tp[0], tp[1], tp[2], tp[3]};
                     if (a.s_pdflat) {
@@ -98,6 +119,9 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(S
                         for (int c = 0; c < RDM_OUT; ++c) a.s_pdflat[out * RDM_OUT + c] = sp[c];
                     }
                     if (a.reward) a.reward[out] = carry;
+                    if constexpr (MIXED) {
+                        if (a.stepped_with) a.stepped_with[out] = coin ? 0.0f : 1.0f;
+                    }
                 }
                 rd::env_time_limit(st, s, episode, a.seed, (uint64_t)(a.env_base + env));   // resets inside its last step
             }

@@ -62,3 +62,11 @@ def episode_loss(values) -> float:
     for v in values:
         total += float(v)
     return total
+
+
+def teacher_share(k: int, warmup_steps: int, beta0: float, beta_decay: float) -> float:
+    """DAgger's beta_i for optimiser step k of the train_envs drivers: beta0 beta_decay^(k - warmup_steps)
+    from the end of the warm-up on, and exactly 0 once that falls below 2^-24, where no coin (a
+    multiple of 2^-24) can fall under it and the plain student launch runs again."""
+    b = float(beta0) * float(beta_decay) ** (int(k) - int(warmup_steps))
+    return b if b >= 2.0 ** -24 else 0.0

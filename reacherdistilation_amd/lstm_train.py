@@ -27,7 +27,7 @@ import torch
 from .config import LSTM_BATCH_SIZE, MAX_CAPACITY, STEPS_UNROLLED, TOTAL_EPISODES
 from .dataset import DeviceDataset
 from .distill import DistillConfig, DistillTrainer
-from .driver_env import DriverEnv, episode_loss
+from .driver_env import DriverEnv, episode_loss, teacher_share
 from .pages import PageStore
 from .policy import TeacherAgent
 from .student_lstm import StudentLstmConfig, StudentLstmTrainer
@@ -117,7 +117,8 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = TOTAL_EP
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-3,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
-               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32"):
+               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32",
+               beta0: float = 0.0, beta_decay: float = 1.0):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -148,11 +149,19 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     the batch no longer follows from the env count (``max_windows`` = replay_windows), and its windows
     come from old and new episodes alike, drawn on the device.  History rows stay per optimiser step
     (the reward that of the act call the step followed); an act call is stepped with the teacher while
-    the optimiser step it precedes is a warm-up step."""
+    the optimiser step it precedes is a warm-up step.
+    ``beta0``, ``beta_decay``: DAgger's mixture pi_i = beta_i pi* + (1 - beta_i) pi^_i instead of the hard
+    switch at ``warmup_steps``: optimiser step k >= warmup_steps is stepped with the teacher share
+    beta = beta0 beta_decay^(k - warmup_steps) (StudentLstmTrainer.set_teacher_share: a coin per env and
+    step, the records' stepped_with its outcome), exactly 0 once below 2^-24; with a ring an act call
+    takes the beta of the optimiser step it precedes.  The defaults (beta0 = 0) are the hard switch,
+    the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K, T = int(n_envs), int(opt_steps), int(accum_steps), STEPS_UNROLLED
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
         raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
+    if not 0.0 <= float(beta0) <= 1.0 or not 0.0 <= float(beta_decay) <= 1.0:
+        raise ValueError("beta0 and beta_decay in [0, 1]")
     if n < 1 or K < 50 or K % 50:
         raise ValueError("n_envs >= 1 and accum_steps a positive multiple of 50")
     cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
@@ -172,6 +181,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
         ring = st.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
     for k in range(steps):
         act_with = "teacher" if k < int(warmup_steps) else "student"
+        if beta0 > 0 and act_with == "student" and (ring is None or k % upa == 0):
+            st.set_teacher_share(teacher_share(k, warmup_steps, beta0, beta_decay))
         if ring is None:
             r = st.step_envs(act_with)
             rew[k] = r.reward.mean()

@@ -34,7 +34,7 @@ from .config import EPISODE_STEPS, LSTM_BATCH_SIZE, MLP_BATCH_SIZE, MLP_EPISODE_
 from .dataset import DeviceDataset
 from .pages import PageStore
 from .distill import DistillConfig, DistillTrainer
-from .driver_env import DriverEnv, episode_loss
+from .driver_env import DriverEnv, episode_loss, teacher_share
 from .policy import TeacherAgent
 from .student_mlp import StudentMlpConfig, StudentMlpTrainer, rows
 
@@ -120,7 +120,8 @@ def train(train: bool = True, restore: bool = False, *, episodes: int = MLP_EPIS
 def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str = "kl", lr: float = 1e-4,
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
-               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0):
+               replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, beta0: float = 0.0,
+               beta_decay: float = 1.0):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -142,11 +143,19 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     50, no training), ring.push_rows of its (accum_steps / 50) n_envs episodes, then ``updates_per_act`` x
     { ring.sample_rows(``replay_windows`` rows, recent=``replay_recent``), step }.  History rows stay per
     optimiser step (the reward that of the act call the step followed); an act call is stepped with the
-    teacher while the optimiser step it precedes is a warm-up step."""
+    teacher while the optimiser step it precedes is a warm-up step.
+    ``beta0``, ``beta_decay``: DAgger's mixture pi_i = beta_i pi* + (1 - beta_i) pi^_i instead of the hard
+    switch at ``warmup_steps``: optimiser step k >= warmup_steps is stepped with the teacher share
+    beta = beta0 beta_decay^(k - warmup_steps) (StudentMlpTrainer.set_teacher_share: a coin per env and
+    step), exactly 0 once below 2^-24; with a ring an act call takes the beta of the optimiser step it
+    precedes, and the records' stepped_with is the per-row flag.  The defaults (beta0 = 0) are the hard
+    switch, the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
         raise ValueError("opt_steps >= 1 and 0 <= warmup_steps <= opt_steps")
+    if not 0.0 <= float(beta0) <= 1.0 or not 0.0 <= float(beta_decay) <= 1.0:
+        raise ValueError("beta0 and beta_decay in [0, 1]")
     cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
     if cap < 0 or (cap and (Bw < 1 or upa < 1 or int(replay_recent) < 0 or K < 50 or K % 50 or n * (K // 50) > cap)):
         raise ValueError("with a replay ring: accum_steps a positive multiple of 50, replay_capacity >= "
@@ -163,13 +172,16 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
         ring = sm.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
     for k in range(steps):
         act_with = "teacher" if k < int(warmup_steps) else "student"
+        if beta0 > 0 and act_with == "student" and (ring is None or k % upa == 0):
+            sm.set_teacher_share(teacher_share(k, warmup_steps, beta0, beta_decay))
         if ring is None:
             r = sm.step_envs(act_with)
             rew[k] = r.reward.mean()
         else:
             if k % upa == 0:
                 r = sm.act_envs(act_with)
-                ring.push_rows(r, stepped_with=float(act_with == "student"))
+                ring.push_rows(r, stepped_with=float(act_with == "student") if sm.stepped_with is None
+                               else sm.stepped_with)
                 mean_reward = r.reward.mean()
             sm.step(*ring.sample_rows(Bw, recent=int(replay_recent)))
             rew[k] = mean_reward

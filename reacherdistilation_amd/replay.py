@@ -50,6 +50,7 @@ nat.register({
     "rd_replay_push_steps": (INT, [P, P, I64, I64]),
     "rd_replay_push_episodes": (INT, [P, P, I64]),
     "rd_replay_push_rows": (INT, [P, P, P, P, P, P, I64, I64, F32]),
+    "rd_replay_push_rows_flags": (INT, [P, P, P, P, P, P, I64, I64, P]),
     "rd_replay_sample_windows": (INT, [P, ctypes.POINTER(RdReplaySample), P, P, P, P, P]),
     "rd_replay_sample_rows": (INT, [P, ctypes.POINTER(RdReplaySample), P, P, P]),
 })
@@ -115,12 +116,14 @@ class ReplayRing:
         nat.check(self._lib.rd_replay_push_episodes(self._h, nat.ptr(r), r.shape[0]), "rd_replay_push_episodes")
         self._keep = r
 
-    def push_rows(self, r, stepped_with: float | None = None):
+    def push_rows(self, r, stepped_with=None):
         """r: a StudentMlpTrainer.act_envs / step_envs result (x [K, n, 16], t_pdflat, s_pdflat, reward
         [K, n]), K a multiple of 50 from an episode's step 0.  The records' rew field is the reward the
         env's previous step returned; the ring keeps ``r.reward[-1]`` as the next call's carry (zeros
-        before the first call and after reset_carry()).  ``stepped_with``: the records' last field
-        (default 1: the student stepped)."""
+        before the first call and after reset_carry()).  ``stepped_with``: the records' last field, one
+        float for every record (default 1: the student stepped) or a [K, n] tensor with a value per
+        record (StudentMlpTrainer.stepped_with after a call under a teacher share;
+        rd_replay_push_rows_flags)."""
         x, t, s, rew = self._f32(r.x), self._f32(r.t_pdflat), self._f32(r.s_pdflat), self._f32(r.reward)
         if x.dim() != 3 or x.shape[2] != ROW or tuple(rew.shape) != tuple(x.shape[:2]) or \
                 tuple(t.shape) != (*x.shape[:2], PDFLAT_SHAPE) or tuple(s.shape) != tuple(t.shape):
@@ -128,13 +131,23 @@ class ReplayRing:
         K, n = x.shape[:2]
         if self._carry is None or self._carry.shape[0] != n:
             self._carry = torch.zeros(n, dtype=torch.float32, device=self.device)
+        flags = None
+        if torch.is_tensor(stepped_with):
+            flags = self._f32(stepped_with)
+            if tuple(flags.shape) != (K, n):
+                raise ValueError(f"a stepped_with tensor must be [K, n] = [{K}, {n}], got {tuple(flags.shape)}")
         self._sync_stream()
-        nat.check(self._lib.rd_replay_push_rows(self._h, nat.ptr(x), nat.ptr(t), nat.ptr(s), nat.ptr(rew),
-                                                nat.ptr(self._carry), K, n,
-                                                1.0 if stepped_with is None else float(stepped_with)),
-                  "rd_replay_push_rows")
+        if flags is not None:
+            nat.check(self._lib.rd_replay_push_rows_flags(self._h, nat.ptr(x), nat.ptr(t), nat.ptr(s), nat.ptr(rew),
+                                                          nat.ptr(self._carry), K, n, nat.ptr(flags)),
+                      "rd_replay_push_rows_flags")
+        else:
+            nat.check(self._lib.rd_replay_push_rows(self._h, nat.ptr(x), nat.ptr(t), nat.ptr(s), nat.ptr(rew),
+                                                    nat.ptr(self._carry), K, n,
+                                                    1.0 if stepped_with is None else float(stepped_with)),
+                      "rd_replay_push_rows")
         self._carry.copy_(rew[K - 1])   # behind the push on the stream
-        self._keep = (x, t, s, rew)
+        self._keep = (x, t, s, rew, flags)
 
     def reset_carry(self):
         """The next push_rows starts from a zero carried reward (after the envs were reset)."""

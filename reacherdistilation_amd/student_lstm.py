@@ -85,6 +85,8 @@ nat.register({
     "rdl_step_envs": _ENVS_TRAIN,
     "rdl_envs_get_state": (INT, [P, P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "rdl_envs_get_query_state": (INT, [P, P]),
+    "rdl_envs_set_teacher_share": (INT, [P, F32, U64]),
+    "rdl_envs_teacher_share": (F32, [P]),
     "rdl_set_teacher": (INT, [P, P, P, P]),
     "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
     "rdl_param_count": (I64, [I32]),
@@ -213,6 +215,7 @@ class StudentLstmTrainer:
         nat.check(self._lib.rdl_set_query_dtype(self._h, qdtype), "rdl_set_query_dtype")
         self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._envs = None     # attach_envs()'s buffers
+        self._envs_seed, self._coin_seed = 0, None   # set_teacher_share
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -443,6 +446,33 @@ class StudentLstmTrainer:
                                 torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None,
                                 torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None)
         self.n_envs, self.accum_steps = n, K
+        self._envs_seed = int(seed)
+        if self._coin_seed is None:   # the coins follow the envs' seed
+            self._set_share(self.teacher_share)
+
+    # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
+    def set_teacher_share(self, beta: float, seed: int | None = None):
+        """The teacher's share beta in [0, 1] of the env steps in act_envs / rollout_envs / step_envs
+        ("student") from the next call on (rdl_envs_set_teacher_share; "teacher" calls ignore it): per env
+        and step a coin, a function of (seed, env_base + i, episode, step) alone -- Philox, word 3 of the
+        counter = 0x80000000 | step, u < beta -- hands the teacher's mean to env.step instead of the
+        student's and writes 0 to the record's stepped_with; everything else of the step ((c, h), the
+        ring, the windows) and the training is the student call's.  ``seed``: the coins' key (default:
+        the envs' seed, whatever attach_envs sets it to).  beta = 0 (the default) is the plain student
+        call.  A captured call keeps the beta it was captured with."""
+        beta = float(beta)
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError(f"beta must be in [0, 1], got {beta}")
+        self._coin_seed = None if seed is None else int(seed)
+        self._set_share(beta)
+
+    def _set_share(self, beta: float):
+        seed = self._envs_seed if self._coin_seed is None else self._coin_seed
+        nat.check(self._lib.rdl_envs_set_teacher_share(self._h, beta, seed % 2 ** 64), "rdl_envs_set_teacher_share")
+
+    @property
+    def teacher_share(self) -> float:
+        return float(self._lib.rdl_envs_teacher_share(self._h))
 
     def reset_envs(self):
         """Every env back to its episode 0; clock, carried reward, query state and history to 0."""

@@ -58,6 +58,9 @@ nat.register({
     "rdm_rollout_envs": _ENVS_CALL,
     "rdm_step_envs": _ENVS_CALL,
     "rdm_envs_get_state": (INT, [P, P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+    "rdm_envs_set_teacher_share": (INT, [P, F32, U64]),
+    "rdm_envs_teacher_share": (F32, [P]),
+    "rdm_envs_bind_stepped_with": (INT, [P, P, I64]),
     "rdm_set_teacher": (INT, [P, P, P, P]),
     "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
@@ -154,6 +157,7 @@ class StudentMlpTrainer:
         self._h = h
         self.teacher = None   # the teacher of evaluate() and of the envs (set_teacher)
         self.n_envs, self.accum_steps, self._envs = 0, 0, None   # attach_envs
+        self._envs_seed, self._coin_seed, self._flags = 0, None, None   # set_teacher_share, stepped_with
         self._grad = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdm_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdm_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed) if params is None else params)
@@ -260,12 +264,14 @@ class StudentMlpTrainer:
         return res
 
     # -- persistent envs: batched on-policy distillation --------------------------------------
-    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 1):
+    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 1,
+                    flags: bool = False):
         """Give the trainer ``n_envs`` persistent lockstep envs (rdm_envs_attach; Philox resets keyed
         (seed, env_base + i, episode)) at episode 0, and allocate once the buffers every
         act_envs / rollout_envs / step_envs call fills: ``accum_steps`` = K env steps per call, so K n
         rows per optimiser step.  K = 50 puts all 50 episode phases of the lockstep envs into every
-        batch.  Attaching again replaces the envs.  Single GPU only."""
+        batch.  Attaching again replaces the envs.  ``flags``: also allocate and bind ``stepped_with``
+        (it is there anyway once a teacher share > 0 is set, and stays once made).  Single GPU only."""
         n, K = int(n_envs), int(accum_steps)
         if n < 1 or K < 1:
             raise ValueError("n_envs >= 1 and accum_steps >= 1")
@@ -280,6 +286,50 @@ class StudentMlpTrainer:
         self._envs = EnvsResult(torch.zeros(K, n, IN_DIM, **kw), torch.zeros(K, n, PDFLAT_SHAPE, **kw),
                                 torch.zeros(K, n, PDFLAT_SHAPE, **kw), torch.zeros(K, n, **kw))
         self.n_envs, self.accum_steps = n, K
+        self._envs_seed = int(seed)
+        if self._coin_seed is None:   # the coins follow the envs' seed
+            self._set_share(self.teacher_share)
+        if flags or self._flags is not None or self.teacher_share > 0:
+            self._bind_flags()
+
+    # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
+    def set_teacher_share(self, beta: float, seed: int | None = None):
+        """The teacher's share beta in [0, 1] of the env steps in act_envs / rollout_envs / step_envs
+        ("student") from the next call on (rdm_envs_set_teacher_share; "teacher" calls ignore it): per env
+        and step a coin, a function of (seed, env_base + i, episode, step) alone -- Philox, word 3 of the
+        counter = 0x80000000 | step, u < beta -- hands the teacher's mean to env.step instead of the
+        student's; everything else of the step, and the training, is the student call's.  ``seed``:
+        the coins' key (default: the envs' seed, whatever attach_envs sets it to).  beta = 0 (the
+        default) is the plain student call.  The first beta > 0 allocates ``stepped_with``.  A captured
+        call keeps the beta it was captured with."""
+        beta = float(beta)
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError(f"beta must be in [0, 1], got {beta}")
+        self._coin_seed = None if seed is None else int(seed)
+        self._set_share(beta)
+        if beta > 0 and self._flags is None and self._envs is not None:
+            self._bind_flags()
+
+    def _set_share(self, beta: float):
+        seed = self._envs_seed if self._coin_seed is None else self._coin_seed
+        nat.check(self._lib.rdm_envs_set_teacher_share(self._h, beta, seed % 2 ** 64), "rdm_envs_set_teacher_share")
+
+    def _bind_flags(self):
+        self._flags = torch.ones(self.accum_steps, self.n_envs, dtype=torch.float32, device=self.device)
+        nat.check(self._lib.rdm_envs_bind_stepped_with(self._h, nat.ptr(self._flags), self._flags.numel()),
+                  "rdm_envs_bind_stepped_with")
+
+    @property
+    def teacher_share(self) -> float:
+        return float(self._lib.rdm_envs_teacher_share(self._h))
+
+    @property
+    def stepped_with(self):
+        """[accum_steps, n] f32, the trainer's own and rewritten by every envs call: 1 where the
+        student's action stepped env i at the call's k-th step, 0 where the teacher's did (all 0 after a
+        "teacher" call); rows past a shorter call's ``steps`` keep their old values.  None until a
+        teacher share > 0 is set or attach_envs(..., flags=True) asks for it."""
+        return self._flags
 
     def reset_envs(self):
         """Every env back to its episode 0; clocks, carried reward and previous fields to 0."""
