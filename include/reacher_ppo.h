@@ -81,6 +81,47 @@ int rdp_bind_grad_buffer(rdp_trainer* t, float* grad);   /* use the caller's buf
 int rdp_get_counter(rdp_trainer* t, int64_t* iterations);
 int rdp_read_metrics(rdp_trainer* t, int64_t count, double* out);   /* [count][RDP_METRICS] */
 
+/* ---- kickstarting: a teacher's KL term in the minibatch loss (Schmitt et al. 2018; policy
+ * distillation's distil-then-fine-tune).  With a teacher set and lambda > 0 a minibatch minimises
+ *   pol_surr + vf_loss + lambda (1/mb) sum_rows KL( pi_theta(.|ob) || pi_T(.|ob) ),
+ * KL in kl_loss's direction (the learner first), per row
+ *   sum_c [ lt_c - ls_c + (exp(2 ls_c) + (mu_c - mut_c)^2) / (2 exp(2 lt_c)) - 1/2 ],
+ * so the head derivatives gain  dmean_c += (lambda/mb) (mu_c - mut_c) / sigmat_c^2  and
+ * dlogstd_c += (lambda/mb) (sigma_c^2 / sigmat_c^2 - 1), on EVERY row of the minibatch, those
+ * whose surrogate gradient the clip has zeroed included; the value net is untouched.
+ * lambda of iteration k = coef max(1 - k S / decay_timesteps, 0), S = n_envs x horizon (the
+ * timestep count of the lrmult schedule), formed in double and rounded to float;
+ * decay_timesteps = 0: the constant coef.
+ * Launches: rdp_rollout appends one (the labels) while a teacher is set; an iteration with
+ * lambda > 0 runs the kickstart instances of the two minibatch kernels and one more single-thread
+ * launch for its metric.  With lambda = 0 (coef 0, the default; a schedule that has reached 0)
+ * rdp_optimize launches exactly what it launches without a teacher.
+ * rdp_reset keeps the teacher and the distillation setting, drops the labels and zeroes the
+ * distillation metrics; the filter returns to its count-1e-2 start as before.
+ * Every call below returns RD_EINVAL, naming the function and the argument, before any device
+ * call (rdp_set_obfilter's std check excepted).  rdp_optimize, and rdp_iterate before its rollout,
+ * return RD_EINVAL if lambda > 0 and the current batch has no labels (no teacher, or the teacher
+ * was set after the rollout). */
+/* the teacher: 2x64 MlpPolicy + its fixed filter, arguments as rdd_set_teacher (device pointers:
+ * params [5060], ob_mean [11], ob_std [11]); the handle keeps its own copy */
+int rdp_set_teacher(rdp_trainer* t, const float* params, const float* ob_mean, const float* ob_std);
+/* host-only (no device call, allocation or sync); coef >= 0 finite, decay_timesteps >= 0 */
+int rdp_set_distill(rdp_trainer* t, float coef, int64_t decay_timesteps);
+float rdp_distill_coef(const rdp_trainer* t);      /* lambda the NEXT rdp_optimize uses; -1 for NULL */
+/* [S][4] = the teacher's mean[2] | logstd[2] on the last rollout's ob rows (t-major, as rdp_get_batch):
+ * bitwise rdd_forward's teacher output on them.  RD_EINVAL without a teacher, or before a rollout
+ * that had it */
+int rdp_get_teacher_labels(rdp_trainer* t, float* t_pdflat);
+/* per iteration, oldest first: [count][2] = mean over the last epoch's minibatches of the minibatch-mean
+ * KL, lambda used (both 0 for an iteration run with lambda = 0); ring of metrics_len like rdp_read_metrics */
+int rdp_read_distill_metrics(rdp_trainer* t, int64_t count, double* out);
+/* seed the RunningMeanStd: sum = mean*count, sumsq = (std^2 + mean^2)*count, count (f64 on the device);
+ * mean [11], std [11] device pointers; count > 0 finite, std > 0 finite, mean finite.  The checks
+ * of mean and std read them back: the call synchronises the stream.  The filter then reads mean and
+ * max(std, 0.1) (the variance floor 1e-2) and goes on updating with every rollout.
+ * rdp_reset returns to the 1e-2 initial state as today. */
+int rdp_set_obfilter(rdp_trainer* t, const float* mean, const float* std, double count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,13 +15,20 @@
 //    backward passes with the weights in LDS, each workgroup keeping its weight-gradient
 //    sums in registers over its tiles; reduce_adam_kernel sums the per-workgroup partial rows
 //    in a fixed order and runs TF1/MpiAdam over the concatenated [pol | vf] vector.  No
-//    atomics: deterministic.
+//    atomics: deterministic;
+//  * kickstarting (rdp_set_teacher / rdp_set_distill): teacher_labels_kernel appends the teacher's
+//    pdflat of the actor batch to the rollout (teacher_f32.h's exact-f32 forward, 16-row tiles),
+//    and an iteration with lambda > 0 runs the <true> instances of the two minibatch kernels, which
+//    add lambda x the minibatch-mean KL(pi || teacher) on the loss lanes; lambda = 0 launches the
+//    <false> instances, the kernels as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <random>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/reacher_ppo.h"
@@ -208,7 +215,10 @@ constexpr int MB_H = MB_R / 2;             // rows per wave in the forward / dat
 constexpr int MB_G = 256;                  // at most this many workgroups (= partial rows)
 constexpr int W2LD = HID + 4;              // LDS row stride of W2 (B operands read both ways)
 constexpr int PSTR = (P_ALL + 3) & ~3;     // partial row stride (floats)
-constexpr int NSTAT = 8;                   // f64 per workgroup: pol_surr, vf_loss, clipfrac, dlogstd0, dlogstd1
+constexpr int NSTAT = 8;                   // f64 per workgroup: pol_surr, vf_loss, clipfrac, dlogstd0, dlogstd1, KL (kickstart)
+constexpr int N_ACC = 5;                   // epoch accumulators: pol_surr, vf_loss, clipfrac, minibatches, KL (kickstart)
+constexpr int KL_STAT = 5, KL_ACC = 4;     // the KL sum's slot in a workgroup's stats / in the epoch accumulators
+static_assert(KL_STAT < NSTAT, "a free stat slot");
 constexpr int RA_COLS = 16, RA_SLICES = 16;   // reduce_adam: 16 columns x 16 row slices per block (32 x 8: +4 %, 64 x 4: +19 %)
 static_assert(RA_COLS * RA_SLICES == 256 && (RA_SLICES & (RA_SLICES - 1)) == 0, "256 threads, power-of-two slices");
 static_assert(MB_R == 32 && HID == 64 && PB1 == OBD * HID && VC1 == OBD * HID,
@@ -230,6 +240,12 @@ struct MbArgs {
     float* part;                            // [G][PSTR]
     double* stat;                           // [G][NSTAT]
     uint32_t* ctl;
+};
+
+// the kickstart instance's arguments: MbArgs, the teacher's labels and lambda
+struct MbKsArgs : MbArgs {
+    const float* tlab;                      // [S][4] the teacher's mean | logstd per actor-batch row
+    float lam;
 };
 
 struct MbLds {
@@ -468,7 +484,10 @@ __global__ __launch_bounds__(256) void logp_old_kernel(const float* params, cons
     }
 }
 
-__global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
+// KS: the kickstart instance, + lambda x the minibatch-mean KL(pi || teacher) (kl_loss's direction,
+// student first) on every row, clipped or not; the plain instance is the kernel as it was
+template <bool KS>
+__global__ __launch_bounds__(256) void minibatch_kernel(std::conditional_t<KS, MbKsArgs, MbArgs> a) {
     __shared__ MbLds L;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int net = w >> 1, half = w & 1, r0 = half * MB_H;
@@ -487,6 +506,7 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
         for (int jb = 0; jb < 4; ++jb) a2[kb][jb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     double ps = 0, vl = 0, cf = 0, g0 = 0, g1 = 0;
+    [[maybe_unused]] double kls = 0;
     const int ntiles = (a.mb + MB_R - 1) / MB_R;
     __syncthreads();
     for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
@@ -507,10 +527,12 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
         const int li = i0 + lane;
         const bool lrow = w < 2 && lane < MB_R && li < a.mb;
         float ac0 = 0, ac1 = 0, lpo = 0, atg = 0, ret = 0;
+        [[maybe_unused]] float4 tp = {0, 0, 0, 0};
         if (lrow) {
             const int64_t p = a.perm[li];
             if (w == 0) {
                 ac0 = a.ac[2 * p]; ac1 = a.ac[2 * p + 1]; lpo = a.lpo[p]; atg = a.atarg[p];
+                if constexpr (KS) tp = *(const float4*)&a.tlab[4 * p];
             } else {
                 ret = a.ret[p];
             }
@@ -543,6 +565,21 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
                 cf += fabsf(ratio - 1.0f) > a.clip_eps ? (double)inv : 0.0;
                 g0 += (double)dlp * (x0 * x0 - 1.0f);
                 g1 += (double)dlp * (x1 * x1 - 1.0f);
+                if constexpr (KS) {
+                    // KL(N(m, sd) || N(tp.xy, exp(tp.zw))) per component = lt - ls + (sd^2 + (m - mt)^2) /
+                    // (2 sdt^2) - 1/2; d/dm = (m - mt) / sdt^2, d/dls = sd^2 / sdt^2 - 1
+                    const float lw = a.lam * inv;
+                    const float it0 = expf(-2.0f * tp.z), it1 = expf(-2.0f * tp.w);
+                    const float e0 = m0 - tp.x, e1 = m1 - tp.y;
+                    const float v0 = sd0 * sd0 * it0, v1 = sd1 * sd1 * it1;
+                    dm0 = fmaf(lw, e0 * it0, dm0);
+                    dm1 = fmaf(lw, e1 * it1, dm1);
+                    g0 += (double)lw * (v0 - 1.0f);
+                    g1 += (double)lw * (v1 - 1.0f);
+                    const float k0 = (tp.z - ls0) + 0.5f * fmaf(e0 * e0, it0, v0) - 0.5f;
+                    const float k1 = (tp.w - ls1) + 0.5f * fmaf(e1 * e1, it1, v1) - 0.5f;
+                    kls += (double)(k0 + k1) * inv;
+                }
             }
             L.dm[lane][0] = dm0;
             L.dm[lane][1] = dm1;
@@ -644,12 +681,65 @@ __global__ __launch_bounds__(256) void minibatch_kernel(MbArgs a) {
     } else if (w == 1) {
         L.red[1][lane] = vl;
     }
-    __syncthreads();
+    if constexpr (KS) {   // the minibatch-mean KL: stat slot KL_STAT, summed by wave 3 beside the five above
+        __shared__ double klr[64];
+        if (w == 0) klr[lane] = kls;
+        __syncthreads();
+        if (tid == 192) {
+            double s = 0.0;
+            for (int l = 0; l < 64; ++l) s += klr[l];
+            a.stat[(int64_t)blockIdx.x * NSTAT + KL_STAT] = s;
+        }
+    } else {
+        __syncthreads();
+    }
     if (tid < 5) {
         double s = 0.0;
         for (int l = 0; l < 64; ++l) s += L.red[tid][l];
         a.stat[(int64_t)blockIdx.x * NSTAT + tid] = s;
     }
+}
+
+#include "teacher_f32.h"   // namespace tch: the teacher's layouts, load_net and mlp_forward
+
+// kickstarting's labels: the teacher's pdflat (mean[2] | logstd[2]) on the actor batch's raw
+// observations under the teacher's own filter.  forward_kernel's teacher half (distill_eval.h): the
+// load_net image, one 16-row tile per wave pass through the wave's obs scratch, mlp_forward<true>;
+// every row's chain is its own, so the labels are bitwise rdd_forward's whatever the grid.
+constexpr int TL_WAVES = 4, TL_GRID = 256;
+static_assert(tch::OBD == OBD && tch::P_TOT == P_POL, "the teacher is a 2x64 MlpPolicy");
+__global__ __launch_bounds__(64 * TL_WAVES) void teacher_labels_kernel(const float* tnet, const float* obs, int64_t S,
+                                                                       float* tflat) {
+    __shared__ __attribute__((aligned(16))) float lds[tch::NET + TL_WAVES * tch::TILE * tch::SOS];
+    tch::load_net(lds, tnet, false, 64 * TL_WAVES);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+    float* ob = lds + tch::NET + wave * tch::TILE * tch::SOS;
+    const int64_t ntiles = (S + tch::TILE - 1) / tch::TILE;
+    for (int64_t t = (int64_t)blockIdx.x * TL_WAVES + wave; t < ntiles; t += (int64_t)gridDim.x * TL_WAVES) {
+        for (int x = lane; x < tch::TILE * tch::SOS; x += 64) {
+            const int e = x / tch::SOS, k = x % tch::SOS;
+            const int64_t i = t * tch::TILE + e;
+            ob[x] = k == OBD ? 1.0f : (i < S ? obs[i * OBD + k] : 0.0f);
+        }
+        rd::wave_sync();
+        const int64_t i = t * tch::TILE + j;
+        f32x4 H1[4], H2[4];
+        float m0, m1;
+        tch::mlp_forward<true>(lds, ob, j, g, H1, H2, m0, m1);
+        if (i < S && g == 0) {
+            tflat[i * 4 + 0] = m0;
+            tflat[i * 4 + 1] = m1;
+            tflat[i * 4 + 2] = lds[tch::N_LS];
+            tflat[i * 4 + 3] = lds[tch::N_LS + 1];
+        }
+        rd::wave_sync();
+    }
+}
+
+// the iteration's distillation metric: the last epoch's mean of the minibatch-mean KL
+__global__ void distill_metric_kernel(const double* acc, float* out) {
+    if (threadIdx.x == 0) out[0] = (float)(acc[KL_ACC] / (acc[3] > 0 ? acc[3] : 1.0));
 }
 
 struct RaArgs {
@@ -668,7 +758,8 @@ struct RaArgs {
 
 // grad[p] = fixed-order sum of the G partial rows (logstd: of the f64 sums), then MpiAdam.update
 // (= TF1 form) over [pol | vf]; t counts minibatch steps.  Block 0 also folds the loss sums into
-// the epoch accumulators (acc: pol_surr, vf_loss, clipfrac, minibatches).
+// the epoch accumulators (acc: pol_surr, vf_loss, clipfrac, minibatches; KS: + the KL sum, column KL_ACC).
+template <bool KS>
 __global__ __launch_bounds__(256) void reduce_adam_kernel(RaArgs a) {
     __shared__ float rs[RA_SLICES][RA_COLS];
     __shared__ double rq[RA_SLICES][RA_COLS];
@@ -687,6 +778,9 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(RaArgs a) {
     }
     if (blockIdx.x == 0 && c < 3)
         for (int b = s; b < a.G; b += RA_SLICES) q += a.stat[(int64_t)b * NSTAT + c];
+    if constexpr (KS)
+        if (blockIdx.x == 0 && c == KL_ACC)
+            for (int b = s; b < a.G; b += RA_SLICES) q += a.stat[(int64_t)b * NSTAT + KL_STAT];
     rs[s][c] = sum;
     rq[s][c] = q;
     __syncthreads();
@@ -723,6 +817,8 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(RaArgs a) {
     if (blockIdx.x == 0) {
         if (a.accumulate && c < 3) a.acc[c] += d0;
         if (a.accumulate && c == 3) a.acc[3] += 1.0;
+        if constexpr (KS)
+            if (a.accumulate && c == KL_ACC) a.acc[KL_ACC] += d0;
         if (c == 0) {
             a.ctl[0] = S + 1u;
             a.ctl[1] = __float_as_uint(b1p * a.b1);
@@ -800,11 +896,26 @@ struct rdp_trainer {
     float* hist = nullptr;
     uint32_t* ctl = nullptr;
     int64_t part_doubles = 0;
+    // kickstarting (rdp_set_teacher / rdp_set_distill); the device buffers are rdp_set_teacher's
+    float* tnet = nullptr;            // the teacher: params [P_POL] | ob mean [11] | ob std [11]
+    float* tlab = nullptr;            // [S][4] its pdflat on the last rollout's ob rows
+    float* dhist = nullptr;           // [metrics_len] the KL of the iterations run with lambda > 0
+    std::vector<float> lam_hist;      // [metrics_len] lambda of every iteration (0: dhist's slot is not read)
+    bool labels_valid = false;        // tlab belongs to the current actor batch and teacher
+    float dcoef = 0.0f;
+    int64_t ddecay = 0;
 };
 
 namespace {
 
 #define RDP_CK(call, what) RD_HIP((call), what)
+
+// lambda of the iteration that starts at t->timesteps: coef max(1 - timesteps / decay, 0), in double
+float distill_lambda(const rdp_trainer* t) {
+    if (!(t->dcoef > 0.0f)) return 0.0f;
+    const double f = t->ddecay > 0 ? fmax(1.0 - t->timesteps / (double)t->ddecay, 0.0) : 1.0;
+    return (float)((double)t->dcoef * f);
+}
 
 int run_rollout(rdp_trainer* t) {
     const int64_t n = t->n, S = t->S;
@@ -835,6 +946,13 @@ int run_rollout(rdp_trainer* t) {
                        (const float*)t->params, (const float*)t->rms, (const float*)t->ob, (const float*)t->ac, S,
                        t->lpo);
     RDP_CK(hipGetLastError(), "rdp filter / logp_old");
+    if (t->tnet) {
+        const int64_t blocks = std::min<int64_t>(((S + tch::TILE - 1) / tch::TILE + TL_WAVES - 1) / TL_WAVES, TL_GRID);
+        hipLaunchKernelGGL(teacher_labels_kernel, dim3((unsigned)blocks), dim3(64 * TL_WAVES), 0, t->stream,
+                           (const float*)t->tnet, (const float*)t->ob, S, t->tlab);
+        RDP_CK(hipGetLastError(), "rdp teacher_labels_kernel");
+        t->labels_valid = true;
+    }
     return RD_OK;
 }
 
@@ -842,17 +960,24 @@ int run_rollout(rdp_trainer* t) {
 // teacher.py:30-36 call leaves it at that default), not tf.train.AdamOptimizer's 1e-8
 constexpr float kAdamEps = 1e-5f;
 
-int minibatch(rdp_trainer* t, const int* perm, bool last_epoch) {
+// lam > 0: the kickstart instances of both kernels; lam == 0: the plain ones, as without a teacher
+int minibatch(rdp_trainer* t, const int* perm, bool last_epoch, float lam) {
     const int mb = t->mb;
     const int ntiles = (mb + MB_R - 1) / MB_R, G = ntiles < MB_G ? ntiles : MB_G;
     MbArgs a{perm, mb, t->params, t->rms, t->ob, t->ac, t->lpo, t->atarg, t->ret,
              t->cfg.clip_param * t->lrmult, t->mbpart, t->mbstat, t->ctl};
-    hipLaunchKernelGGL(minibatch_kernel, dim3((unsigned)G), dim3(256), 0, t->stream, a);
+    if (lam > 0.0f) {
+        MbKsArgs k{a, t->tlab, lam};
+        hipLaunchKernelGGL(minibatch_kernel<true>, dim3((unsigned)G), dim3(256), 0, t->stream, k);
+    } else {
+        hipLaunchKernelGGL(minibatch_kernel<false>, dim3((unsigned)G), dim3(256), 0, t->stream, a);
+    }
     RDP_CK(hipGetLastError(), "rdp minibatch_kernel");
     RaArgs r{t->mbpart, t->mbstat, G, t->grad, t->params, t->m, t->v, t->ctl, t->acc, last_epoch ? 1 : 0,
              t->cfg.optim_stepsize * t->lrmult, 0.9f, 0.999f, kAdamEps};
-    hipLaunchKernelGGL(reduce_adam_kernel, dim3((P_ALL + RA_COLS - 1) / RA_COLS), dim3(RA_SLICES * RA_COLS), 0,
-                       t->stream, r);
+    const dim3 rg((P_ALL + RA_COLS - 1) / RA_COLS), rb(RA_SLICES * RA_COLS);
+    if (lam > 0.0f) hipLaunchKernelGGL(reduce_adam_kernel<true>, rg, rb, 0, t->stream, r);
+    else hipLaunchKernelGGL(reduce_adam_kernel<false>, rg, rb, 0, t->stream, r);
     RDP_CK(hipGetLastError(), "rdp reduce_adam_kernel");
     return RD_OK;
 }
@@ -882,10 +1007,16 @@ int run_optimize(rdp_trainer* t) {
     RDP_CK(hipMemcpyAsync(t->perm, t->host_perm[cur].data(), sizeof(int) * (size_t)E * S, hipMemcpyHostToDevice,
                           t->stream),
            "rdp perm");
-    RDP_CK(hipMemsetAsync(t->acc, 0, sizeof(double) * 4, t->stream), "rdp acc");
+    const float lam = distill_lambda(t);   // > 0: rdp_optimize has checked the labels
+    const int64_t slot = (int64_t)(t->iter % (uint32_t)t->cfg.metrics_len);
+    RDP_CK(hipMemsetAsync(t->acc, 0, sizeof(double) * (lam > 0.0f ? N_ACC : 4), t->stream), "rdp acc");
     for (int e = 0; e < E; ++e)
         for (int b = 0; b < nmb; ++b)
-            if (int rc = minibatch(t, t->perm + (int64_t)e * S + (int64_t)b * t->mb, e == E - 1)) return rc;
+            if (int rc = minibatch(t, t->perm + (int64_t)e * S + (int64_t)b * t->mb, e == E - 1, lam)) return rc;
+    t->lam_hist[(size_t)slot] = lam;
+    if (lam > 0.0f)
+        hipLaunchKernelGGL(distill_metric_kernel, dim3(1), dim3(64), 0, t->stream, (const double*)t->acc,
+                           t->dhist + slot);
     t->timesteps += (double)S;
     hipLaunchKernelGGL(metrics_kernel, dim3(1), dim3(64), 0, t->stream, (const double*)t->stats,
                        (const double*)t->acc, (const float*)t->params, t->lrmult, t->timesteps,
@@ -932,6 +1063,7 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
     t->S = S;
     t->mb = cfg->optim_batchsize > 0 ? cfg->optim_batchsize : (int)S;
     for (auto& h : t->host_perm) h.resize((size_t)cfg->optim_epochs * S);
+    t->lam_hist.assign((size_t)t->cfg.metrics_len, 0.0f);
     const int64_t n = t->n;
     rd::DeviceAllocs& mem = t->mem;
     mem.stream = t->stream;
@@ -948,7 +1080,7 @@ int rdp_create(rdp_trainer** out, const rdp_config* cfg, int device, void* hip_s
     t->part_doubles = 2 * OBD * ((S + RB * 8 - 1) / (RB * 8) + 1) + 5 * ((S + RB - 1) / RB + 1) + 4 * ((n + RB - 1) / RB + 1);
     ad(&t->part, t->part_doubles);
     ad(&t->stats, 4);
-    ad(&t->acc, 4);
+    ad(&t->acc, N_ACC);
     af(&t->rms, 2 * OBD);
     ai(&t->perm, (int64_t)cfg->optim_epochs * S);
     af(&t->mbpart, (int64_t)MB_G * PSTR);
@@ -1026,6 +1158,9 @@ int rdp_reset(rdp_trainer* t) {
     t->perm_for = UINT32_MAX;
     t->timesteps = 0.0;
     t->lrmult = 1.0f;
+    // the teacher and the distillation setting stay; the labels and the distillation metrics go
+    t->labels_valid = false;
+    std::fill(t->lam_hist.begin(), t->lam_hist.end(), 0.0f);
     return RD_OK;
 }
 
@@ -1038,14 +1173,125 @@ int rdp_rollout(rdp_trainer* t) {
 
 int rdp_optimize(rdp_trainer* t) {
     if (!t) return rd::set_error(RD_EINVAL, "rdp_optimize: null handle");
+    if (distill_lambda(t) > 0.0f && !t->labels_valid)
+        return rd::set_error(RD_EINVAL, "rdp_optimize: distill coef %g > 0 but the current batch has no teacher labels "
+                             "(rdp_set_teacher, then rdp_rollout)", (double)distill_lambda(t));
     rd::DeviceGuard dg(t->device);
     RD_HIP(dg.err, "rdp_optimize");
     return run_optimize(t);
 }
 
 int rdp_iterate(rdp_trainer* t) {
+    if (t && distill_lambda(t) > 0.0f && !t->tnet)
+        return rd::set_error(RD_EINVAL, "rdp_iterate: distill coef %g > 0 but no teacher is set (rdp_set_teacher)",
+                             (double)distill_lambda(t));
     if (int rc = rdp_rollout(t)) return rc;
     return rdp_optimize(t);
+}
+
+int rdp_set_teacher(rdp_trainer* t, const float* params, const float* ob_mean, const float* ob_std) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdp_set_teacher: null handle");
+    if (!params) return rd::set_error(RD_EINVAL, "rdp_set_teacher: null params");
+    if (!ob_mean) return rd::set_error(RD_EINVAL, "rdp_set_teacher: null ob_mean");
+    if (!ob_std) return rd::set_error(RD_EINVAL, "rdp_set_teacher: null ob_std");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_set_teacher");
+    if (!t->tnet) {   // the first teacher brings the kickstart buffers
+        rd::DeviceAllocs& mem = t->mem;
+        mem.stream = t->stream;
+        float *tnet = nullptr, *tlab = nullptr, *dhist = nullptr;
+        mem.zeroed(&tnet, (size_t)(P_POL + 2 * OBD));
+        mem.zeroed(&tlab, (size_t)(4 * t->S));
+        mem.zeroed(&dhist, (size_t)t->cfg.metrics_len);
+        if (mem.err != hipSuccess) {   // what was allocated stays on the handle's list for rdp_destroy
+            const hipError_t e = mem.err;
+            mem.err = hipSuccess;
+            return rd::hip_fail(e, "rdp_set_teacher: allocation");
+        }
+        t->tlab = tlab;
+        t->dhist = dhist;
+        t->tnet = tnet;
+    }
+    t->labels_valid = false;   // the batch's labels, if any, are another teacher's
+    return rd::upload_net("rdp_set_teacher", t->tnet, params, P_POL, ob_mean, ob_std, OBD, t->stream);
+}
+
+int rdp_set_distill(rdp_trainer* t, float coef, int64_t decay_timesteps) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdp_set_distill: null handle");
+    if (!(coef >= 0.0f) || !std::isfinite(coef))
+        return rd::set_error(RD_EINVAL, "rdp_set_distill: coef %g is not a finite number >= 0", (double)coef);
+    if (decay_timesteps < 0)
+        return rd::set_error(RD_EINVAL, "rdp_set_distill: decay_timesteps %lld < 0", (long long)decay_timesteps);
+    t->dcoef = coef;
+    t->ddecay = decay_timesteps;
+    return RD_OK;
+}
+
+float rdp_distill_coef(const rdp_trainer* t) { return t ? distill_lambda(t) : -1.0f; }
+
+int rdp_get_teacher_labels(rdp_trainer* t, float* t_pdflat) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdp_get_teacher_labels: null handle");
+    if (!t_pdflat) return rd::set_error(RD_EINVAL, "rdp_get_teacher_labels: null t_pdflat");
+    if (!t->tnet) return rd::set_error(RD_EINVAL, "rdp_get_teacher_labels: no teacher is set (rdp_set_teacher)");
+    if (!t->labels_valid)
+        return rd::set_error(RD_EINVAL, "rdp_get_teacher_labels: no rollout since the teacher was set (rdp_rollout)");
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_get_teacher_labels");
+    RD_HIP(hipMemcpyAsync(t_pdflat, t->tlab, sizeof(float) * 4 * t->S, hipMemcpyDeviceToDevice, t->stream),
+           "rdp_get_teacher_labels");
+    return RD_OK;
+}
+
+int rdp_read_distill_metrics(rdp_trainer* t, int64_t count, double* out) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdp_read_distill_metrics: null handle");
+    if (!out) return rd::set_error(RD_EINVAL, "rdp_read_distill_metrics: null out");
+    if (count < 0) return rd::set_error(RD_EINVAL, "rdp_read_distill_metrics: count %lld < 0", (long long)count);
+    const int64_t len = t->cfg.metrics_len, steps = t->iter;
+    if (count > steps || count > len)
+        return rd::set_error(RD_EINVAL, "rdp_read_distill_metrics: only %lld iterations kept",
+                             (long long)(steps < len ? steps : len));
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_read_distill_metrics");
+    std::vector<float> kl((size_t)len, 0.0f);
+    if (t->dhist) {   // read behind the stream's work, as rdp_read_metrics
+        RD_HIP(hipStreamSynchronize(t->stream), "rdp_read_distill_metrics");
+        RD_HIP(hipMemcpy(kl.data(), t->dhist, sizeof(float) * (size_t)len, hipMemcpyDeviceToHost),
+               "rdp_read_distill_metrics");
+    }
+    for (int64_t k = 0; k < count; ++k) {
+        const size_t s = (size_t)((steps - count + k) % len);
+        const float lam = t->lam_hist[s];
+        out[2 * k] = lam > 0.0f ? (double)kl[s] : 0.0;
+        out[2 * k + 1] = (double)lam;
+    }
+    return RD_OK;
+}
+
+int rdp_set_obfilter(rdp_trainer* t, const float* mean, const float* std, double count) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdp_set_obfilter: null handle");
+    if (!mean) return rd::set_error(RD_EINVAL, "rdp_set_obfilter: null mean");
+    if (!std) return rd::set_error(RD_EINVAL, "rdp_set_obfilter: null std");
+    if (!(count > 0.0) || !std::isfinite(count))
+        return rd::set_error(RD_EINVAL, "rdp_set_obfilter: count %g is not a finite number > 0", count);
+    rd::DeviceGuard dg(t->device);
+    RD_HIP(dg.err, "rdp_set_obfilter");
+    float h[2 * OBD];
+    RD_HIP(hipMemcpyAsync(h, mean, sizeof(float) * OBD, hipMemcpyDeviceToHost, t->stream), "rdp_set_obfilter");
+    RD_HIP(hipMemcpyAsync(h + OBD, std, sizeof(float) * OBD, hipMemcpyDeviceToHost, t->stream), "rdp_set_obfilter");
+    RD_HIP(hipStreamSynchronize(t->stream), "rdp_set_obfilter");
+    double sums[2 * OBD + 1];
+    for (int k = 0; k < OBD; ++k) {
+        const double m = h[k], sd = h[OBD + k];
+        if (!std::isfinite(m)) return rd::set_error(RD_EINVAL, "rdp_set_obfilter: mean[%d] = %g is not finite", k, m);
+        if (!(sd > 0.0) || !std::isfinite(sd))
+            return rd::set_error(RD_EINVAL, "rdp_set_obfilter: std[%d] = %g is not a finite number > 0", k, sd);
+        sums[k] = m * count;
+        sums[OBD + k] = (sd * sd + m * m) * count;
+    }
+    sums[2 * OBD] = count;
+    RD_HIP(hipMemcpyAsync(t->rms_sums, sums, sizeof(sums), hipMemcpyHostToDevice, t->stream), "rdp_set_obfilter");
+    RD_HIP(hipStreamSynchronize(t->stream), "rdp_set_obfilter");   // `sums` is this frame's
+    return RD_OK;
 }
 
 int rdp_get_batch(rdp_trainer* t, float* ob, float* ac, float* vpred, float* rew, float* newf, float* nextvpred,

@@ -7,6 +7,11 @@ stochastic policy, GAE(lambda), advantage standardization, observation-filter up
 old-policy freeze, ``optim_epochs`` epochs of shuffled minibatch Adam steps.  The trained
 policy is a 2x64 MlpPolicy in the distillation layout (``teacher()`` returns it with its
 filter), so it drops into ``DistillTrainer`` / ``TeacherAgent`` as the teacher.
+
+Kickstarting: ``set_teacher`` + ``set_distill(coef, decay_timesteps)`` add
+lambda x KL(pi || teacher) to every minibatch's loss (every row, clipped or not), and
+``set_obfilter`` seeds the observation filter so that a policy's weights can be carried into
+PPO together with the normalisation they were trained under (``train(init=..., init_filter_count=...)``).
 """
 from __future__ import annotations
 
@@ -51,6 +56,12 @@ nat.register({
     "rdp_bind_grad_buffer": (INT, [P, P]),
     "rdp_get_counter": (INT, [P, ctypes.POINTER(I64)]),
     "rdp_read_metrics": (INT, [P, I64, P]),
+    "rdp_set_teacher": (INT, [P, P, P, P]),
+    "rdp_set_distill": (INT, [P, F32, I64]),
+    "rdp_distill_coef": (F32, [P]),
+    "rdp_get_teacher_labels": (INT, [P, P]),
+    "rdp_read_distill_metrics": (INT, [P, I64, P]),
+    "rdp_set_obfilter": (INT, [P, P, P, ctypes.c_double]),
 })
 
 
@@ -159,6 +170,43 @@ class PPOTrainer:
         nat.check(self._lib.rdp_get_obfilter(self._h, nat.ptr(mean), nat.ptr(std)), "rdp_get_obfilter")
         return mean, std
 
+    def set_obfilter(self, mean, std, count: float):
+        """Seed the running observation statistics with (mean, std) at weight ``count``: the
+        filter then reads mean and max(std, 0.1) and goes on updating with every rollout."""
+        m, s = self._dev(mean, OBD), self._dev(std, OBD)
+        self._sync_stream()
+        nat.check(self._lib.rdp_set_obfilter(self._h, nat.ptr(m), nat.ptr(s), float(count)), "rdp_set_obfilter")
+
+    # -- kickstarting ------------------------------------------------------------------
+    def set_teacher(self, p: MlpPolicyParams):
+        """The teacher of the KL term (a 2x64 MlpPolicy with its fixed filter); the trainer copies it."""
+        f, mu, sd = p.device_tensors(self.device)
+        self._sync_stream()
+        nat.check(self._lib.rdp_set_teacher(self._h, nat.ptr(f), nat.ptr(mu), nat.ptr(sd)), "rdp_set_teacher")
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def set_distill(self, coef: float, decay_timesteps: int = 0):
+        """lambda of iteration k = coef max(1 - k S / decay_timesteps, 0); 0 timesteps: constant."""
+        nat.check(self._lib.rdp_set_distill(self._h, float(coef), int(decay_timesteps)), "rdp_set_distill")
+
+    def distill_coef(self) -> float:
+        """lambda the next optimize() uses."""
+        return float(self._lib.rdp_distill_coef(self._h))
+
+    def teacher_labels(self) -> torch.Tensor:
+        """[T, n, 4]: the teacher's mean | logstd on the last rollout's observations."""
+        out = torch.empty(self.cfg.horizon, self.cfg.n_envs, 4, device=self.device)
+        self._sync_stream()
+        nat.check(self._lib.rdp_get_teacher_labels(self._h, nat.ptr(out)), "rdp_get_teacher_labels")
+        return out
+
+    def distill_metrics(self, count: int = 1) -> np.ndarray:
+        """[count, 2] per iteration, oldest first: the last epoch's mean KL, lambda."""
+        out = np.zeros((count, 2), np.float64)
+        nat.check(self._lib.rdp_read_distill_metrics(self._h, count, out.ctypes.data_as(ctypes.c_void_p)),
+                  "rdp_read_distill_metrics")
+        return out
+
     def teacher(self) -> MlpPolicyParams:
         """The current policy with its observation filter, in the distillation layout."""
         mean, std = self.obfilter()
@@ -207,13 +255,29 @@ class PPOTrainer:
 
 
 def train(env_id: str = "Reacher-v2", num_timesteps: int = 1_000_000, seed: int = 0, device="cuda:0", log=print,
-          **kw) -> PPOTrainer:
-    """teacher.train (reference teacher.py:23-37): PPO until num_timesteps env steps."""
+          teacher: MlpPolicyParams | None = None, distill_coef: float = 0.0, distill_timesteps: int = 0,
+          init: MlpPolicyParams | None = None, init_filter_count: float = 0.0, **kw) -> PPOTrainer:
+    """teacher.train (reference teacher.py:23-37): PPO until num_timesteps env steps.
+
+    Kickstarting: ``teacher`` with ``distill_coef`` > 0 adds lambda x KL(pi || teacher) to every
+    minibatch's loss, lambda = distill_coef max(1 - timesteps / distill_timesteps, 0) (0: constant).
+    ``init``: the policy starts from its weights; with ``init_filter_count`` > 0 its observation
+    filter seeds the running statistics at that weight (without it the weights meet differently
+    normalised inputs from the first rollout on)."""
     if env_id != "Reacher-v2":
         raise ValueError("only Reacher-v2 is built")
-    tr = PPOTrainer(PPOConfig(seed=seed, max_timesteps=num_timesteps, **kw), device=device)
+    tr = PPOTrainer(PPOConfig(seed=seed, max_timesteps=num_timesteps, **kw), device=device, policy=init)
+    if init is not None and init_filter_count > 0:
+        tr.set_obfilter(init.ob_mean, init.ob_std, init_filter_count)
+    if teacher is not None:
+        tr.set_teacher(teacher)
+    tr.set_distill(distill_coef, distill_timesteps)
     while tr.iterations() * tr.S < num_timesteps:
         tr.iterate()
         m = tr.metrics(1)[0]
-        log(" ".join(f"{k}={v:.4g}" for k, v in zip(METRICS, m)))
+        line = " ".join(f"{k}={v:.4g}" for k, v in zip(METRICS, m))
+        if teacher is not None:
+            kl, lam = tr.distill_metrics(1)[0]
+            line += f" distill_kl={kl:.4g} distill_coef={lam:.4g}"
+        log(line)
     return tr
