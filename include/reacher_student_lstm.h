@@ -66,6 +66,7 @@
 #include <stdint.h>
 
 #include "reacher.h"
+#include "reacher_action_noise.h"   /* rd_action_noise: rdl_envs_set_action_noise, rdl_evaluate_noisy */
 
 #ifdef __cplusplus
 extern "C" {
@@ -314,6 +315,41 @@ int rdl_envs_get_query_state(rdl_trainer* t, float* state_out);
  * read: NULL trainer; beta NaN, < 0 or > 1.  rdl_envs_teacher_share returns beta, -1 for NULL. */
 int rdl_envs_set_teacher_share(rdl_trainer* t, float beta, uint64_t coin_seed);
 float rdl_envs_teacher_share(const rdl_trainer* t);
+
+/* Action noise in the envs calls above (reacher_action_noise.h has the definition): the handle has an
+ * rd_action_noise; the default mode = RD_NOISE_NONE, and a set back to it, with no actions buffer
+ * bound leaves every call exactly as described above (the same launch of the same kernel).
+ * Otherwise, in rdl_envs_act / rdl_rollout_envs / rdl_step_envs under BOTH RDL_ACT_STUDENT (with the
+ * beta-coin as it is) and RDL_ACT_TEACHER (DART's noisy expert; the student is still not evaluated),
+ * the action handed to env.step is the perturbed mean of whoever acts at that step -- S_s, T_s under
+ * RDL_ACT_TEACHER, T_s where the coin fell -- at e = env_base + i and the env's device clock
+ * (episode, s).  ONLY that action changes: the records (both pdflats, stepped_with), (c, h), the
+ * history ring, the windows and the training on every window are as without noise.  The noise is a
+ * function of (seed, env, episode, step) alone: it does not depend on the grid or the split of the
+ * steps over calls, and a captured call replays the NEXT steps' noise.  Mode, scale and seed are
+ * kernel arguments: a captured call keeps the values it was captured with, whatever is set later.
+ * rdl_envs_set_action_noise is host-only, like rdl_envs_set_teacher_share; the next call takes the new
+ * setting; it may precede rdl_envs_attach and survives attach and reset.  rdl_evaluate never reads
+ * it.  RD_EINVAL, naming the function and the field, before the handle is read: NULL trainer or
+ * struct; unknown mode; scale NaN, negative or infinite.
+ * rdl_envs_action_noise copies the setting to *out (RD_EINVAL for a NULL trainer or out). */
+int rdl_envs_set_action_noise(rdl_trainer* t, const rd_action_noise* nz);
+int rdl_envs_action_noise(const rdl_trainer* t, rd_action_noise* out);
+/* Where the action that stepped each env goes: buf = a caller-owned device buffer [K][n_envs][2] of
+ * `rows` rows, step-major as reward; every later call of either actor fills its steps x n_envs rows
+ * (the acting means when the noise is off).  buf = NULL unbinds.  Host-only.  While a buffer is bound
+ * a call with steps x n_envs > rows is RD_EINVAL naming `rows`; so are a NULL trainer and rows < 1
+ * with a buffer here. */
+int rdl_envs_bind_actions(rdl_trainer* t, float* buf /*[K][n][2] step-major*/, int64_t rows);
+
+/* rdl_evaluate with the student's action perturbed by *nz (RD_NOISE_POLICY or RD_NOISE_FIXED) at
+ * Philox episode first_episode + e, with or without a draws table: the records, returns, final_dist
+ * and state_out of the noisy trajectory (records keep S_s, not the action).  Bitwise the stepwise loop
+ * with rd_perturb_actions between rdl_forward and rd_step.  Independent of the envs' noise setting.
+ * RD_EINVAL as rdl_evaluate, and before it: NULL nz, unknown mode, a bad scale, mode = RD_NOISE_NONE
+ * (call rdl_evaluate). */
+int rdl_evaluate_noisy(rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
+                       float* returns, float* final_dist, float* records, float* state_out);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "reacher.h"
+#include "reacher_action_noise.h"   /* rd_action_noise: rdm_envs_set_action_noise, rdm_evaluate_noisy */
 #include "reacher_replay.h"   /* rd_replay: rd_replay_push_rows_flags, below */
 
 #ifdef __cplusplus
@@ -236,6 +237,40 @@ int rdm_envs_bind_stepped_with(rdm_trainer* t, float* buf, int64_t rows);
 int rd_replay_push_rows_flags(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat,
                               const float* reward, const float* carry, int64_t steps, int64_t n_envs,
                               const float* stepped_with_rows);
+
+/* Action noise in the envs calls above (reacher_action_noise.h has the definition): the handle has an
+ * rd_action_noise; the default mode = RD_NOISE_NONE, and a set back to it, with no actions buffer
+ * bound leaves every call exactly as described above (the same launch of the same kernel).
+ * Otherwise, in rdm_envs_act / rdm_rollout_envs / rdm_step_envs under BOTH RDM_ACT_STUDENT (with the
+ * beta-coin as it is) and RDM_ACT_TEACHER (DART's noisy expert; the student is still not evaluated),
+ * the action handed to env.step is the perturbed mean of whoever acts at that step -- S_s, T_s under
+ * RDM_ACT_TEACHER, T_s where the coin fell -- at e = env_base + i and the env's device clock
+ * (episode, s).  ONLY that action changes: x, t_pdflat, s_pdflat, stepped_with and the training on
+ * every row are as without noise.  The noise is a function of (seed, env, episode, step) alone: it
+ * does not depend on the grid, the block size or the split of the steps over calls, and a captured
+ * call replays the NEXT steps' noise.  Mode, scale and seed are kernel arguments: a captured call
+ * keeps the values it was captured with, whatever is set later.
+ * rdm_envs_set_action_noise is host-only (no device call, no allocation, no synchronisation); the
+ * next call takes the new setting; it may precede rdm_envs_attach and survives attach and reset.
+ * rdm_evaluate never reads it.  RD_EINVAL, naming the function and the field, before the handle is
+ * read: NULL trainer or struct; unknown mode; scale NaN, negative or infinite.
+ * rdm_envs_action_noise copies the setting to *out (RD_EINVAL for a NULL trainer or out). */
+int rdm_envs_set_action_noise(rdm_trainer* t, const rd_action_noise* nz);
+int rdm_envs_action_noise(const rdm_trainer* t, rd_action_noise* out);
+/* Where the action that stepped each env goes: buf = a caller-owned device buffer [K][n_envs][2] of
+ * `rows` rows, step-major as reward; every later call of either actor fills its steps x n_envs rows
+ * (the acting means when the noise is off).  buf = NULL unbinds.  Host-only; `rows` is checked as
+ * rdm_envs_bind_stepped_with checks it. */
+int rdm_envs_bind_actions(rdm_trainer* t, float* buf /*[K][n][2] step-major*/, int64_t rows);
+
+/* rdm_evaluate with the student's action perturbed by *nz (RD_NOISE_POLICY or RD_NOISE_FIXED) at
+ * Philox episode first_episode + e, with or without a draws table: the records, returns and final_dist
+ * of the noisy trajectory (records keep S_s, not the action).  Bitwise the stepwise loop with
+ * rd_perturb_actions between rdm_forward and rd_step.  Independent of the envs' noise setting.
+ * RD_EINVAL as rdm_evaluate, and before it: NULL nz, unknown mode, a bad scale, mode = RD_NOISE_NONE
+ * (call rdm_evaluate). */
+int rdm_evaluate_noisy(rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz,
+                       float* returns, float* final_dist, float* records);
 
 #ifdef __cplusplus
 }

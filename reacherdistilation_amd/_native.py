@@ -26,6 +26,12 @@ INT = ctypes.c_int
 RD_RESET_PHILOX = 0
 RD_RESET_TABLE = 1
 
+
+class RdActionNoise(ctypes.Structure):
+    """rd_action_noise (include/reacher_action_noise.h); action_noise.py builds and checks one"""
+    _fields_ = [("mode", I32), ("scale", F32), ("seed", U64)]
+
+
 # (name, restype, argtypes) for every symbol include/*.h declares
 SIGNATURES = {
     # reacher.h
@@ -41,6 +47,8 @@ SIGNATURES = {
     "rd_crc32c": (ctypes.c_uint32, [P, I64, ctypes.c_uint32]),
     "rd_version": (ctypes.c_char_p, []),
     "rd_last_error": (ctypes.c_char_p, []),
+    # reacher_action_noise.h
+    "rd_perturb_actions": (INT, [ctypes.POINTER(RdActionNoise), I64, I64, I32, I32, P, P, P, INT, P]),
     # reacher_comm.h
     "rd_comm_unique_id": (INT, [P]),
     "rd_comm_probe": (INT, [INT]),

@@ -304,6 +304,42 @@ __device__ __forceinline__ bool teacher_coin(uint64_t coin_seed, uint64_t env_id
     return u01(o[0]) < beta;
 }
 
+// Action noise of the acting policy (include/reacher_action_noise.h, the one definition): the two
+// normal draws of env `env_id` at step `step` of its episode, Box-Muller on words 0 and 1 of
+// Philox(ctr = env_id lo, env_id hi, episode, 0x40000000 | step; key = seed).  Counter word 3 has
+// bit 30 set and bit 31 clear: disjoint from the reset draws (0, 1) and the coins (bit 31) under one
+// seed.  One f32 operation per statement: every kernel that inlines it draws the same bits.
+__device__ __forceinline__ void action_noise_draw(uint64_t seed, uint64_t env_id, int32_t episode, int32_t step,
+                                                  float& xi0, float& xi1) {
+    FP_SOURCE_ROUNDING();
+    uint32_t o[4];
+    philox((uint32_t)env_id, (uint32_t)(env_id >> 32), (uint32_t)episode, 0x40000000u | (uint32_t)step,
+           (uint32_t)seed, (uint32_t)(seed >> 32), o);
+    const float u1 = (float)((o[0] >> 8) + 1u) * (1.0f / 16777216.0f);   // (0, 1]
+    const float u2 = u01(o[1]);
+    const float l = logf(u1);
+    const float rad = sqrtf(-2.0f * l);
+    const float ang = 6.283185307179586f * u2;
+    const float c = cosf(ang), s = sinf(ang);
+    xi0 = rad * c;
+    xi1 = rad * s;
+}
+
+// The action that steps the env: the acting pdflat's mean (m0, m1), perturbed by the draws under
+// `mode` (RD_NOISE_*: 0 none, 1 the policy's own exp(logstd), 2 a fixed sigma) and `scale`
+__device__ __forceinline__ void action_noise_apply(int32_t mode, float scale, float xi0, float xi1, float m0, float m1,
+                                                   float ls0, float ls1, float& a0, float& a1) {
+    FP_SOURCE_ROUNDING();
+    a0 = m0;
+    a1 = m1;
+    if (mode != 0) {
+        const float e0 = mode == 1 ? expf(ls0) : 1.0f, e1 = mode == 1 ? expf(ls1) : 1.0f;
+        const float g0 = scale * e0, g1 = scale * e1;
+        a0 = __fmaf_rn(g0, xi0, m0);
+        a1 = __fmaf_rn(g1, xi1, m1);
+    }
+}
+
 // ------------------------------------------------------------------ envs a handle keeps on the device
 // (persistent envs: state [8][n], AUX rows of carried values [AUX][n], clock [2][n] = step of the
 // episode, episode.  student_lstm_envs.h calls these; student_mlp_envs.h has the same two bodies

@@ -29,7 +29,8 @@
 //
 // One translation unit: the device code is the ten student_lstm_*.h included below, in the order the
 // kernels stand in the object.  This file keeps rdl_trainer, the choice of launches for a batch
-// (Path), one function per cell path and head path, and the C ABI.
+// (Path), one function per cell path and head path, and the C ABI.  (The envs and evaluation kernels'
+// noisy instances, action noise, are compiled in student_lstm_noise.hip: student_lstm_noise.h.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -39,11 +40,13 @@
 #include <new>
 
 #include "../../include/reacher_student_lstm.h"
+#include "rd_action_noise.h"
 #include "rd_common.h"
 #include "rd_device.h"
 #include "rd_gemm.h"
 #include "rd_host.h"
 #include "rd_physics.h"
+#include "student_lstm_noise.h"
 
 namespace {
 
@@ -114,6 +117,11 @@ struct rdl_trainer {
     // handle, not of its envs -- attach and reset leave them
     float beta = 0.0f;         // the teacher's share of the env steps
     uint64_t coin_seed = 0;
+    // action noise in the envs calls (rdl_envs_set_action_noise, rdl_envs_bind_actions): host-side
+    // settings of the handle too
+    rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
+    float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
+    int64_t action_rows = 0;
 };
 
 namespace {
@@ -598,6 +606,10 @@ int envs_check(const char* fn, const rdl_trainer* t, int act_with, int steps, co
                                         "of history", fn, t->T, EV_MAX_T);
     if (t->envs.n > ((int64_t)1 << 31) / steps)
         return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs.n);
+    if (t->actions && (int64_t)steps * t->envs.n > t->action_rows)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the actions buffer "
+                                        "(rdl_envs_bind_actions)", fn, steps, (long long)t->envs.n,
+                             (long long)t->action_rows);
     if (train) {
         if (steps % rd::kEpisodeSteps)
             return rd::set_error(RD_EINVAL, "%s: steps %d is not a multiple of the episode's %d", fn, steps,
@@ -632,6 +644,14 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
     auto* kern = !stu ? student_lstm_envs_kernel<false, false>
                  : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
+    // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
+    // wants the actions (student_lstm_noise.hip); they carry the mixture too
+    if (t->noise.mode != RD_NOISE_NONE || t->actions) {
+        const rd::LstmEnvsNoiseLaunch l{&a, stu, t->beta, t->coin_seed, t->noise, t->actions, bf16_query(t), grid.x,
+                                        t->stream};
+        RD_HIP(rd::launch_lstm_envs_noisy(l), "student_lstm_envs_kernel (noisy) launch");
+        return RD_OK;
+    }
     // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0);
     // otherwise the launch above, with the arguments it always had
     if (stu && t->beta > 0.0f) {
@@ -938,20 +958,25 @@ int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, c
     return RD_OK;
 }
 
-int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
-                 float* records, float* state_out) {
-    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "rdl_evaluate: null trainer, config or returns");
+}  // extern "C"
+
+namespace {
+
+// rdl_evaluate (nz = null) and rdl_evaluate_noisy, `fn` naming the caller
+int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
+             float* returns, float* final_dist, float* records, float* state_out) {
+    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "%s: null trainer, config or returns", fn);
     if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
-        return rd::set_error(RD_EINVAL, "rdl_evaluate: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
-    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "rdl_evaluate: episodes %d < 1", cfg->episodes);
+        return rd::set_error(RD_EINVAL, "%s: n_envs %lld outside 1 .. 2^31", fn, (long long)cfg->n_envs);
+    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "%s: episodes %d < 1", fn, cfg->episodes);
     if (cfg->env_base < 0 || cfg->first_episode < 0 || cfg->grid < 0)
-        return rd::set_error(RD_EINVAL, "rdl_evaluate: negative env_base, first_episode or grid");
-    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "rdl_evaluate: no teacher set (rdl_set_teacher)");
+        return rd::set_error(RD_EINVAL, "%s: negative env_base, first_episode or grid", fn);
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdl_set_teacher)", fn);
     if (t->T > EV_MAX_T)
-        return rd::set_error(RD_EINVAL, "rdl_evaluate: %d unrolled steps, the kernel keeps at most %d records of history",
+        return rd::set_error(RD_EINVAL, "%s: %d unrolled steps, the kernel keeps at most %d records of history", fn,
                              t->T, EV_MAX_T);
     rd::DeviceGuard dg(t->device);
-    RD_HIP(dg.err, "rdl_evaluate");
+    RD_HIP(dg.err, fn);
     if (int rc = launch_eval_pack(t)) return rc;
     LsEvalArgs a;
     a.n = cfg->n_envs;
@@ -971,10 +996,30 @@ int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0
     a.T = t->T;
     // a block of 16 envs per workgroup for the whole launch, one workgroup per CU (its LDS)
     const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = cfg->grid > 0 ? cfg->grid : t->cus;
+    if (nz) {   // the noisy instances (student_lstm_noise.hip)
+        const rd::LstmEvalNoiseLaunch l{&a, *nz, bf16_query(t), (unsigned)(nblk < cap ? nblk : cap), t->stream};
+        RD_HIP(rd::launch_lstm_eval_noisy(l), "student_lstm_evaluate_kernel (noisy) launch");
+        return RD_OK;
+    }
     auto* kern = bf16_query(t) ? student_lstm_evaluate_kernel<true> : student_lstm_evaluate_kernel<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
     return RD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
+                 float* records, float* state_out) {
+    return evaluate("rdl_evaluate", t, cfg, nullptr, state0, returns, final_dist, records, state_out);
+}
+
+int rdl_evaluate_noisy(rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
+                       float* returns, float* final_dist, float* records, float* state_out) {
+    if (int rc = rd::check_action_noise("rdl_evaluate_noisy", nz, false)) return rc;
+    return evaluate("rdl_evaluate_noisy", t, cfg, nz, state0, returns, final_dist, records, state_out);
 }
 
 int rdl_envs_reset(rdl_trainer* t) {
@@ -1039,6 +1084,27 @@ int rdl_envs_set_teacher_share(rdl_trainer* t, float beta, uint64_t coin_seed) {
 }
 
 float rdl_envs_teacher_share(const rdl_trainer* t) { return t ? t->beta : -1.0f; }
+
+int rdl_envs_set_action_noise(rdl_trainer* t, const rd_action_noise* nz) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_action_noise: null trainer");
+    if (int rc = rd::check_action_noise("rdl_envs_set_action_noise", nz, true)) return rc;
+    t->noise = *nz;
+    return RD_OK;
+}
+
+int rdl_envs_action_noise(const rdl_trainer* t, rd_action_noise* out) {
+    if (!t || !out) return rd::set_error(RD_EINVAL, "rdl_envs_action_noise: null trainer or out");
+    *out = t->noise;
+    return RD_OK;
+}
+
+int rdl_envs_bind_actions(rdl_trainer* t, float* buf, int64_t rows) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_bind_actions: null trainer");
+    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdl_envs_bind_actions: rows %lld < 1", (long long)rows);
+    t->actions = buf;
+    t->action_rows = buf ? rows : 0;
+    return RD_OK;
+}
 
 int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode) {
     if (!t || !state) return rd::set_error(RD_EINVAL, "rdl_envs_get_state: null trainer or state");

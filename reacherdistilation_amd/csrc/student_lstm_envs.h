@@ -64,6 +64,18 @@ struct LsEnvsMixArgs : LsEnvsArgs {
     uint64_t coin_seed;      // the coins' Philox key
 };
 
+// the noisy instances' (rdl_envs_set_action_noise, rdl_envs_bind_actions), compiled in
+// student_lstm_noise.hip.  Again a struct of its own; the instances are told by it (kNoisy), so the
+// kernel's template parameters, and with them every other instance's name, stay as they are
+struct LsEnvsNoiseArgs : LsEnvsMixArgs {
+    int32_t noise_mode;      // RD_NOISE_* (include/reacher_action_noise.h)
+    float noise_scale;
+    uint64_t noise_seed;     // the noise's Philox key
+    float* actions;          // [K][n][2] or null: the action that stepped the env
+};
+template <class ARGS> constexpr bool kNoisy = false;
+template <> constexpr bool kNoisy<LsEnvsNoiseArgs> = true;
+
 // episode 0 of every env; clock and aux to 0 (rd_reset's arithmetic); q and hist are memset by the host
 __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -77,6 +89,11 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
 // coin in the env's lane (rd::teacher_coin: a function of (coin seed, env, episode, step) alone, so
 // known before the step and drawn before its first barrier) that hands the teacher's T_s[0..1] to
 // env_step instead of S_s[0..1]; the record's stepped_with is 1 - coin.
+// kNoisy<ARGS> (action noise; a student instance is then MIXED too, beta = 0 never firing; the teacher
+// instance is not): the two normal draws of this env and step in the env's lane, beside the coin
+// (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
+// T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
+// Nothing else of the step changes: the record, (c, h), the ring and the windows are the plain call's.
 template <bool STUDENT_ACTS, bool BF16Q, bool MIXED = false, class ARGS = LsEnvsArgs>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
     static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
@@ -128,6 +145,8 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             if (phys) {   // record s, and its raw prev = T_{s-1} (zero at s = 0) into the ring
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
+                if constexpr (kNoisy<ARGS>)
+                    ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), episode, s);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) lds::Xr[slot][lane][EH_PREV + c] = s ? lds::TO[(s - 1) & 1][lane][c] : 0.0f;
                 if constexpr (MIXED) ls_record_head(lane, slot, st, rec, carry, coin ? 0.0f : 1.0f);
@@ -165,7 +184,19 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             if (phys) {
                 float sp[4];
                 ls_record_tail<STUDENT_ACTS>(lane, s, rec, tp, sp);
-                if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
+                if constexpr (kNoisy<ARGS>) {
+                    const bool tch_acts = MIXED ? coin : !STUDENT_ACTS;
+                    const float xi0 = ls_noise_park()[2 * lane], xi1 = ls_noise_park()[2 * lane + 1];
+                    float a0, a1;
+                    rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, tch_acts ? tp[0] : sp[0],
+                                           tch_acts ? tp[1] : sp[1], tch_acts ? tp[2] : sp[2], tch_acts ? tp[3] : sp[3],
+                                           a0, a1);
+                    carry = rd::env_step<true>(st, a0, a1);
+                    if (valid && a.actions) {
+                        a.actions[((int64_t)k * n + env) * 2] = a0;
+                        a.actions[((int64_t)k * n + env) * 2 + 1] = a1;
+                    }
+                } else if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
                 else carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
                 if (valid && a.reward) a.reward[(int64_t)k * n + env] = carry;
             }

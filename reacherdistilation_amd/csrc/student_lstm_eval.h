@@ -31,8 +31,19 @@ struct LsEvalArgs {
 };
 
 // BF16Q: the positions run on the bf16 cell (student_lstm_query_bf16.h; a.img is then the handle's WF image)
-template <bool BF16Q>
-__global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(LsEvalArgs a) {
+// rdl_evaluate_noisy's instances (student_lstm_noise.hip), told by their argument struct: the student's
+// action perturbed (include/reacher_action_noise.h) at Philox episode first_episode + e, with or
+// without a draws table; the draws are taken in the env's lane before the step's first barrier
+struct LsEvalNoiseArgs : LsEvalArgs {
+    int32_t noise_mode;      // RD_NOISE_POLICY or RD_NOISE_FIXED
+    float noise_scale;
+    uint64_t noise_seed;
+};
+template <class ARGS> constexpr bool kNoisyEval = false;
+template <> constexpr bool kNoisyEval<LsEvalNoiseArgs> = true;
+
+template <bool BF16Q, class ARGS = LsEvalArgs>
+__global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS a) {
     const LsThread q = ls_prologue(a.tnet, a.P, a.img, a.T);
     const int tid = q.tid, lane = q.lane, T = q.T;
     const bool phys = q.wave == 0 && lane < EV_ROWS;   // the env of this lane
@@ -63,6 +74,9 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(LsEva
             for (int s = 0; s < rd::kEpisodeSteps; ++s) {
                 const int slot = s % T;
                 float* rec = rec0 ? rec0 + s * EV_REC : nullptr;
+                if constexpr (kNoisyEval<ARGS>) {
+                    if (phys) ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s);
+                }
                 if (phys) ls_record_head(lane, slot, st, rec, carry, 1.0f);
                 // prev . Wp + bp of record s: prev = T_{s-1}, zero at s = 0
                 lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
@@ -75,7 +89,14 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(LsEva
                 if (phys) {
                     float sp[4], tp[4];
                     ls_record_tail(lane, s, rec, tp, sp);
-                    carry = rd::env_step<true>(st, sp[0], sp[1]);
+                    if constexpr (kNoisyEval<ARGS>) {
+                        const float xi0 = ls_noise_park()[2 * lane], xi1 = ls_noise_park()[2 * lane + 1];
+                        float a0, a1;
+                        rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, sp[0], sp[1], sp[2], sp[3], a0, a1);
+                        carry = rd::env_step<true>(st, a0, a1);
+                    } else {
+                        carry = rd::env_step<true>(st, sp[0], sp[1]);
+                    }
                     ret += carry;
                 }
             }

@@ -306,3 +306,20 @@ __device__ __forceinline__ void ls_record_tail(int lane, int s, float* rec, floa
         }
     }
 }
+
+// The noisy instances' draws (action noise, include/reacher_action_noise.h; student_lstm_noise.hip):
+// taken in the env's lane before the step's first barrier, so that Philox and Box-Muller run beside
+// the positions, and parked in LDS until ls_record_tail's side of the step -- the kernels run at the
+// register limit, and two more values live across the step moved a spill's reload into an f32 MFMA's
+// SrcC window (scripts/isa/hazards.py LDSRC).  The lane reads back what it wrote: no barrier.  Only
+// the instances that call these carry the 128 bytes.
+__device__ __forceinline__ float* ls_noise_park() {
+    __shared__ float xi[EV_ROWS * 2];
+    return xi;
+}
+__device__ __forceinline__ void ls_noise_draw(int lane, uint64_t seed, uint64_t env_id, int32_t episode, int32_t step) {
+    float xi0, xi1;
+    rd::action_noise_draw(seed, env_id, episode, step, xi0, xi1);
+    ls_noise_park()[2 * lane] = xi0;
+    ls_noise_park()[2 * lane + 1] = xi1;
+}

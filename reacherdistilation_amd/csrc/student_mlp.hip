@@ -27,7 +27,8 @@
 // in student_mlp_eval.h, the persistent envs of the batched on-policy step (rdm_step_envs) in
 // student_mlp_envs.h, their common step in student_mlp_query.h.  This file keeps rdm_trainer, the
 // choice of the row block, one launch function per kernel family, and the C ABI.  (The envs kernel's
-// mixed instances, DAgger's beta-mixture, are compiled in student_mlp_mix.hip: student_mlp_mix.h.)
+// mixed instances, DAgger's beta-mixture, are compiled in student_mlp_mix.hip: student_mlp_mix.h; the
+// envs and evaluation kernels' noisy instances in student_mlp_noise.hip: student_mlp_noise.h.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -35,11 +36,13 @@
 #include <new>
 
 #include "../../include/reacher_student_mlp.h"
+#include "rd_action_noise.h"
 #include "rd_common.h"
 #include "rd_device.h"
 #include "rd_host.h"
 #include "rd_physics.h"
 #include "student_mlp_mix.h"
+#include "student_mlp_noise.h"
 
 namespace {
 
@@ -91,6 +94,11 @@ struct rdm_trainer {
     uint64_t coin_seed = 0;
     float* flags = nullptr;     // the caller's stepped_with buffer [flag_rows], or null
     int64_t flag_rows = 0;
+    // action noise in the envs calls (rdm_envs_set_action_noise, rdm_envs_bind_actions): host-side
+    // settings of the handle too
+    rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
+    float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
+    int64_t action_rows = 0;
 };
 
 namespace {
@@ -228,6 +236,10 @@ int envs_check(const char* fn, const rdm_trainer* t, int act_with, int steps, co
         return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the stepped_with buffer "
                                         "(rdm_envs_bind_stepped_with)", fn, steps, (long long)t->envs.n,
                              (long long)t->flag_rows);
+    if (t->actions && (int64_t)steps * t->envs.n > t->action_rows)
+        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the actions buffer "
+                                        "(rdm_envs_bind_actions)", fn, steps, (long long)t->envs.n,
+                             (long long)t->action_rows);
     return RD_OK;
 }
 
@@ -245,6 +257,17 @@ int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdfl
     auto* kern = stu && t->bf ? (b.small ? student_mlp_envs_kernel<16, true, true> : student_mlp_envs_kernel<64, true, true>)
                  : b.small    ? (stu ? student_mlp_envs_kernel<16, true, false> : student_mlp_envs_kernel<16, false, false>)
                               : (stu ? student_mlp_envs_kernel<64, true, false> : student_mlp_envs_kernel<64, false, false>);
+    // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
+    // wants the actions (student_mlp_noise.hip); they carry the mixture too
+    if (t->noise.mode != RD_NOISE_NONE || t->actions) {
+        if (!stu && t->flags)   // the teacher stepped every row
+            RD_HIP(hipMemsetAsync(t->flags, 0, sizeof(float) * (size_t)steps * (size_t)a.n, t->stream),
+                   "student_mlp_envs_kernel: stepped_with");
+        const rd::MlpEnvsNoiseLaunch l{&a, stu, t->beta, t->coin_seed, t->flags, t->noise, t->actions, t->bf, b.small,
+                                       b.grid, b.threads, t->stream};
+        RD_HIP(rd::launch_mlp_envs_noisy(l), "student_mlp_envs_kernel (noisy) launch");
+        return RD_OK;
+    }
     // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0) or a
     // stepped_with buffer wants its flags; otherwise the launch above, with the arguments it always had
     if (stu && (t->beta > 0.0f || t->flags)) {
@@ -444,16 +467,22 @@ int rdm_set_teacher(rdm_trainer* t, const float* params, const float* ob_mean, c
     return RD_OK;
 }
 
-int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records) {
-    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "rdm_evaluate: null trainer, config or returns");
+}  // extern "C"
+
+namespace {
+
+// rdm_evaluate (nz = null) and rdm_evaluate_noisy, `fn` naming the caller
+int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz, float* returns,
+             float* final_dist, float* records) {
+    if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "%s: null trainer, config or returns", fn);
     if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
-        return rd::set_error(RD_EINVAL, "rdm_evaluate: n_envs %lld outside 1 .. 2^31", (long long)cfg->n_envs);
-    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "rdm_evaluate: episodes %d < 1", cfg->episodes);
+        return rd::set_error(RD_EINVAL, "%s: n_envs %lld outside 1 .. 2^31", fn, (long long)cfg->n_envs);
+    if (cfg->episodes < 1) return rd::set_error(RD_EINVAL, "%s: episodes %d < 1", fn, cfg->episodes);
     if (cfg->env_base < 0 || cfg->first_episode < 0 || cfg->grid < 0)
-        return rd::set_error(RD_EINVAL, "rdm_evaluate: negative env_base, first_episode or grid");
-    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "rdm_evaluate: no teacher set (rdm_set_teacher)");
+        return rd::set_error(RD_EINVAL, "%s: negative env_base, first_episode or grid", fn);
+    if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdm_set_teacher)", fn);
     rd::DeviceGuard dg(t->device);
-    RD_HIP(dg.err, "rdm_evaluate");
+    RD_HIP(dg.err, fn);
     SmEvalArgs a;
     a.n = cfg->n_envs;
     a.env_base = cfg->env_base;
@@ -468,11 +497,30 @@ int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, flo
     a.first_episode = cfg->first_episode;
     // a block of envs per workgroup for the whole launch, sized as rdm_forward sizes its row block
     const Blocks b = blocks_of(a.n, cfg->grid > 0 ? cfg->grid : t->grid, eval_small_rows, true);
+    if (nz) {   // the noisy instances (student_mlp_noise.hip)
+        const rd::MlpEvalNoiseLaunch l{&a, *nz, t->bf, b.small, b.grid, b.threads, t->stream};
+        RD_HIP(rd::launch_mlp_eval_noisy(l), "student_mlp_evaluate_kernel (noisy) launch");
+        return RD_OK;
+    }
     auto* kern = t->bf ? (b.small ? student_mlp_evaluate_kernel<16, true> : student_mlp_evaluate_kernel<64, true>)
                        : (b.small ? student_mlp_evaluate_kernel<16, false> : student_mlp_evaluate_kernel<64, false>);
     hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
     RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
     return RD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records) {
+    return evaluate("rdm_evaluate", t, cfg, nullptr, returns, final_dist, records);
+}
+
+int rdm_evaluate_noisy(rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz, float* returns,
+                       float* final_dist, float* records) {
+    if (int rc = rd::check_action_noise("rdm_evaluate_noisy", nz, false)) return rc;
+    return evaluate("rdm_evaluate_noisy", t, cfg, nz, returns, final_dist, records);
 }
 
 int rdm_envs_reset(rdm_trainer* t) {
@@ -534,6 +582,27 @@ int rdm_envs_bind_stepped_with(rdm_trainer* t, float* buf, int64_t rows) {
     if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_stepped_with: rows %lld < 1", (long long)rows);
     t->flags = buf;
     t->flag_rows = buf ? rows : 0;
+    return RD_OK;
+}
+
+int rdm_envs_set_action_noise(rdm_trainer* t, const rd_action_noise* nz) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_action_noise: null trainer");
+    if (int rc = rd::check_action_noise("rdm_envs_set_action_noise", nz, true)) return rc;
+    t->noise = *nz;
+    return RD_OK;
+}
+
+int rdm_envs_action_noise(const rdm_trainer* t, rd_action_noise* out) {
+    if (!t || !out) return rd::set_error(RD_EINVAL, "rdm_envs_action_noise: null trainer or out");
+    *out = t->noise;
+    return RD_OK;
+}
+
+int rdm_envs_bind_actions(rdm_trainer* t, float* buf, int64_t rows) {
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_bind_actions: null trainer");
+    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_actions: rows %lld < 1", (long long)rows);
+    t->actions = buf;
+    t->action_rows = buf ? rows : 0;
     return RD_OK;
 }
 

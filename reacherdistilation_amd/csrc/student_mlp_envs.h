@@ -46,6 +46,18 @@ struct SmEnvsMixArgs : SmEnvsArgs {
     float* stepped_with;     // [K][n] or null: 1 where the student's action stepped the env, else 0
 };
 
+// the noisy instances' (rdm_envs_set_action_noise, rdm_envs_bind_actions), compiled in
+// student_mlp_noise.hip.  Again a struct of its own; the instances are told by it (kNoisy), so the
+// kernel's template parameters, and with them every other instance's name, stay as they are
+struct SmEnvsNoiseArgs : SmEnvsMixArgs {
+    int32_t noise_mode;      // RD_NOISE_* (include/reacher_action_noise.h)
+    float noise_scale;
+    uint64_t noise_seed;     // the noise's Philox key
+    float* actions;          // [K][n][2] or null: the action that stepped the env
+};
+template <class ARGS> constexpr bool kNoisy = false;
+template <> constexpr bool kNoisy<SmEnvsNoiseArgs> = true;
+
 // episode 0 of every env; clocks, carried reward and previous fields to 0 (rd_reset's arithmetic)
 __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -61,12 +73,18 @@ __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs 
 // (coin seed, env, episode, step) alone, drawn before the step's first barrier so that it runs beside
 // the layers -- that hands the teacher's T_s[0..1] to env_step instead of S_s[0..1].  x, t_pdflat and
 // s_pdflat are written as the student instance writes them; the coin goes to stepped_with.
+// kNoisy<ARGS> (action noise; a student instance is then MIXED too, beta = 0 never firing; a teacher
+// instance is not): the two normal draws of this env and step in the env's lane, beside the coin
+// (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
+// T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
+// Nothing else of the step changes.
 template <int ROWS, bool STUDENT_ACTS, bool BF, bool MIXED = false, class ARGS = SmEnvsArgs>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(ARGS a) {
     // MIXED: the teacher steps this lane's env now.  The kernel's first local: declared inside the step
     // loop it moves hipcc's layout of the six instances that never read it
     // (profiles/envs_teacher_share_isa.txt)
     bool coin = false;
+    float xi0 = 0.0f, xi1 = 0.0f;   // kNoisy: this step's draws, declared here for the same reason
     __shared__ __attribute__((aligned(16))) float lds[ELay<ROWS>::LDS_FLOATS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
     tch::load_net(lds + ELay<ROWS>::O_NET, a.tnet, false, ELay<ROWS>::THREADS);   // published by the first step's barriers
@@ -96,6 +114,8 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(A
             if (phys) {
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
+                if constexpr (kNoisy<ARGS>)
+                    rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), episode, s, xi0, xi1);
                 float row[RDM_IN];
                 qs_row<ROWS, STUDENT_ACTS>(lds, lane, st, s, tp, prev_field, row);
                 if (valid) {
@@ -110,7 +130,18 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(A
             if (phys) {
                 float sp[RDM_OUT];
                 qs_outputs<ROWS, STUDENT_ACTS>(lds, lane, sp, tp);
-                if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
+                if constexpr (kNoisy<ARGS>) {
+                    const bool tch_acts = MIXED ? coin : !STUDENT_ACTS;
+                    float a0, a1;
+                    rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, tch_acts ? tp[0] : sp[0],
+                                           tch_acts ? tp[1] : sp[1], tch_acts ? tp[2] : sp[2], tch_acts ? tp[3] : sp[3],
+                                           a0, a1);
+                    carry = rd::env_step<true>(st, a0, a1);
+                    if (valid && a.actions) {
+                        a.actions[out * 2] = a0;
+                        a.actions[out * 2 + 1] = a1;
+                    }
+                } else if constexpr (MIXED) carry = rd::env_step<true>(st, coin ? tp[0] : sp[0], coin ? tp[1] : sp[1]);
                 else carry = STUDENT_ACTS ? rd::env_step<true>(st, sp[0], sp[1]) : rd::env_step<true>(st, tp[0], tp[1]);
                 if (valid) {
                     *reinterpret_cast<f32x4*>(a.t_pdflat + out * RDM_OUT) = f32x4{tp[0], tp[1], tp[2], tp[3]};

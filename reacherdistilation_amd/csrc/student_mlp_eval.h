@@ -23,8 +23,22 @@ struct SmEvalArgs {
     int episodes, first_episode;
 };
 
-template <int ROWS, bool BF>
-__global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kernel(SmEvalArgs a) {
+// rdm_evaluate_noisy's instances (student_mlp_noise.hip), told by their argument struct: the student's
+// action perturbed (include/reacher_action_noise.h) at Philox episode first_episode + e, with or
+// without a draws table; the draws are taken in the env's lane before the step's first barrier
+struct SmEvalNoiseArgs : SmEvalArgs {
+    int32_t noise_mode;      // RD_NOISE_POLICY or RD_NOISE_FIXED
+    float noise_scale;
+    uint64_t noise_seed;
+};
+template <class ARGS> constexpr bool kNoisyEval = false;
+template <> constexpr bool kNoisyEval<SmEvalNoiseArgs> = true;
+
+template <int ROWS, bool BF, class ARGS = SmEvalArgs>
+__global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kernel(ARGS a) {
+    // kNoisyEval: the step's draws.  The kernel's first locals, as student_mlp_envs_kernel's coin is:
+    // declared inside the step loop they move hipcc's register names in the four plain instances
+    float xi0 = 0.0f, xi1 = 0.0f;
     __shared__ __attribute__((aligned(16))) float lds[ELay<ROWS>::LDS_FLOATS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
     tch::load_net(lds + ELay<ROWS>::O_NET, a.tnet, false, ELay<ROWS>::THREADS);   // published by the first step's barriers
@@ -52,6 +66,8 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
             float* rec = a.records && valid ? a.records + ((int64_t)e * n + env) * (rd::kEpisodeSteps * EREC) : nullptr;
             for (int s = 0; s < rd::kEpisodeSteps; ++s) {
                 if (phys) {
+                    if constexpr (kNoisyEval<ARGS>)
+                        rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s, xi0, xi1);
                     float row[RDM_IN];
                     qs_row<ROWS, true>(lds, lane, st, s, tp, prev_field, row);
                     if (rec) {
@@ -63,7 +79,9 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                     }
                     prev_field = carry;
                 }
-                qs_layers<ROWS, true, BF, false>(lds, a.img, wave, i, g);
+                // (the noisy instances run layer 1 fenced, as the envs kernel does: unfenced, the 64-env f32
+                // one had the loads into an in-flight MFMA's SrcC that student_mlp_envs.h describes)
+                qs_layers<ROWS, true, BF, kNoisyEval<ARGS>>(lds, a.img, wave, i, g);
                 if (phys) {
                     float sp[RDM_OUT];
                     qs_outputs<ROWS, true>(lds, lane, sp, tp);
@@ -75,7 +93,13 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                             r[RDM_OUT + c] = sp[c];
                         }
                     }
-                    carry = rd::env_step<true>(st, sp[0], sp[1]);
+                    if constexpr (kNoisyEval<ARGS>) {
+                        float a0, a1;
+                        rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, sp[0], sp[1], sp[2], sp[3], a0, a1);
+                        carry = rd::env_step<true>(st, a0, a1);
+                    } else {
+                        carry = rd::env_step<true>(st, sp[0], sp[1]);
+                    }
                     ret += carry;
                 }
             }

@@ -118,7 +118,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32",
-               beta0: float = 0.0, beta_decay: float = 1.0):
+               beta0: float = 0.0, beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -155,7 +155,11 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     beta = beta0 beta_decay^(k - warmup_steps) (StudentLstmTrainer.set_teacher_share: a coin per env and
     step, the records' stepped_with its outcome), exactly 0 once below 2^-24; with a ring an act call
     takes the beta of the optimiser step it precedes.  The defaults (beta0 = 0) are the hard switch,
-    the same launches as before."""
+    the same launches as before.
+    ``noise``, ``noise_scale``: action noise in every envs call of the run, warm-up steps included
+    (StudentLstmTrainer.set_action_noise, keyed by ``seed``): "fixed" with the teacher acting
+    (warmup_steps = opt_steps) is DART's noisy expert, "policy" samples whoever acts.  The evaluations
+    stay noiseless.  The default "none" is the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K, T = int(n_envs), int(opt_steps), int(accum_steps), STEPS_UNROLLED
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
@@ -173,6 +177,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                                               metrics_len=steps, dtype=dtype, query_dtype=query_dtype), device=device)
     st.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     st.attach_envs(n, seed=seed, accum_steps=K)
+    if noise != "none":
+        st.set_action_noise(noise, noise_scale)
     rew = torch.zeros(steps, device=st.device)
     evals = []
     ring = None

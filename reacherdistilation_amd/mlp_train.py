@@ -121,7 +121,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, beta0: float = 0.0,
-               beta_decay: float = 1.0):
+               beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -149,7 +149,11 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     beta = beta0 beta_decay^(k - warmup_steps) (StudentMlpTrainer.set_teacher_share: a coin per env and
     step), exactly 0 once below 2^-24; with a ring an act call takes the beta of the optimiser step it
     precedes, and the records' stepped_with is the per-row flag.  The defaults (beta0 = 0) are the hard
-    switch, the same launches as before."""
+    switch, the same launches as before.
+    ``noise``, ``noise_scale``: action noise in every envs call of the run, warm-up steps included
+    (StudentMlpTrainer.set_action_noise, keyed by ``seed``): "fixed" with the teacher acting
+    (warmup_steps = opt_steps) is DART's noisy expert, "policy" samples whoever acts.  The evaluations
+    stay noiseless.  The default "none" is the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
@@ -164,6 +168,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                                             dtype=dtype), device=device)
     sm.set_teacher(teacher if teacher is not None else synthetic_teacher(DistillConfig().teacher_seed))
     sm.attach_envs(n, seed=seed, accum_steps=K)
+    if noise != "none":
+        sm.set_action_noise(noise, noise_scale)
     rew = torch.zeros(steps, device=sm.device)
     evals = []
     ring = None

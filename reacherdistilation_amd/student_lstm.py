@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import action_noise as an
 from .config import LSTM_BATCH_SIZE, NUM_UNITS, OBSPACE_SHAPE, PDFLAT_SHAPE, STEPS_UNROLLED
 from .dist import allreduce_sum_
 from .distill import EvalResult
@@ -87,6 +88,10 @@ nat.register({
     "rdl_envs_get_query_state": (INT, [P, P]),
     "rdl_envs_set_teacher_share": (INT, [P, F32, U64]),
     "rdl_envs_teacher_share": (F32, [P]),
+    "rdl_envs_set_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
+    "rdl_envs_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
+    "rdl_envs_bind_actions": (INT, [P, P, I64]),
+    "rdl_evaluate_noisy": (INT, [P, ctypes.POINTER(RdlEvalConfig), ctypes.POINTER(nat.RdActionNoise), P, P, P, P, P]),
     "rdl_set_teacher": (INT, [P, P, P, P]),
     "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
     "rdl_param_count": (I64, [I32]),
@@ -216,6 +221,7 @@ class StudentLstmTrainer:
         self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._envs = None     # attach_envs()'s buffers
         self._envs_seed, self._coin_seed = 0, None   # set_teacher_share
+        self._noise, self._noise_seed, self._actions = ("none", 1.0), None, None   # set_action_noise, actions
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -372,7 +378,8 @@ class StudentLstmTrainer:
 
     def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
                  first_episode: int = 0, draws=None, state0=None, final_dist: bool = False, records: bool = False,
-                 final_state: bool = False, grid: int = 0) -> EvalResult:
+                 final_state: bool = False, grid: int = 0, noise: str = "none", noise_scale: float = 1.0,
+                 noise_seed: int | None = None) -> EvalResult:
         """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
         with this student's mean action in ONE rollout launch (rdl_evaluate): the query loop of
         lstm_train.train without the optimiser steps, each env being column B-1 of the driver's
@@ -388,7 +395,13 @@ class StudentLstmTrainer:
         without a table, from Philox(seed, env_base + i, first_episode + e).  Returns a
         distill.EvalResult: returns [E, n]; final_dist [E, n]; records [E, n, 50, 21] in the dataset's
         layout (stepped_with = 1); state [2, n, 200] = (c, h) after the last query with
-        ``final_state``.  Asynchronous on the current stream; no allocation in the library: capturable."""
+        ``final_state``.  Asynchronous on the current stream; no allocation in the library: capturable.
+        ``noise`` = "policy" or "fixed" (rdl_evaluate_noisy; action_noise.py): the student's action is
+        perturbed, a = mean + noise_scale (exp(logstd) | 1) xi with xi keyed (noise_seed, env_base + i,
+        first_episode + e, step) -- the return under perturbed actions, bitwise the stepwise loop with
+        action_noise.perturb_actions before the step.  ``noise_seed`` defaults to ``seed``.  The envs'
+        set_action_noise is never read here: the default is the noiseless return."""
+        nz = an.native(noise, noise_scale, seed if noise_seed is None else noise_seed)
         n, E = int(n_envs), int(episodes)
         if n < 1 or E < 1:
             raise ValueError("n_envs >= 1 and episodes >= 1")
@@ -412,22 +425,28 @@ class StudentLstmTrainer:
                           first_episode=int(first_episode), grid=int(grid),
                           draws=table.data_ptr() if table is not None else None)
         self._sync_stream()
-        nat.check(self._lib.rdl_evaluate(self._h, ctypes.byref(c), nat.ptr(state0) if state0 is not None else None,
-                                         nat.ptr(res.returns), nat.ptr(res.final_dist) if final_dist else None,
-                                         nat.ptr(res.records) if records else None,
-                                         nat.ptr(res.state) if final_state else None), "rdl_evaluate")
+        out = (nat.ptr(state0) if state0 is not None else None, nat.ptr(res.returns),
+               nat.ptr(res.final_dist) if final_dist else None, nat.ptr(res.records) if records else None,
+               nat.ptr(res.state) if final_state else None)
+        if noise == "none":
+            nat.check(self._lib.rdl_evaluate(self._h, ctypes.byref(c), *out), "rdl_evaluate")
+        else:
+            nat.check(self._lib.rdl_evaluate_noisy(self._h, ctypes.byref(c), ctypes.byref(nz), *out),
+                      "rdl_evaluate_noisy")
         self._keep_eval = (table, state0)   # the launch reads them asynchronously
         return res
 
     # -- persistent envs: batched on-policy distillation --------------------------------------
-    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 50):
+    def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 50,
+                    actions: bool = False):
         """Give the trainer ``n_envs`` persistent lockstep envs (rdl_envs_attach; Philox resets keyed
         (seed, env_base + i, episode)) at episode 0 with a zero query state, and allocate once the
         buffers every act_envs / rollout_envs / step_envs call fills: ``accum_steps`` = K env steps
         per call at the most.  A call of a multiple of 50 steps holds n (K / 50) (51 - T) training
         windows (any 50 consecutive lockstep steps hold 51 - T queries whose window lies inside one
         episode); ``max_windows`` of the config must cover that for the training calls.  Attaching
-        again replaces the envs.  Single GPU only."""
+        again replaces the envs.  ``actions``: also allocate and bind ``actions``, the action that
+        stepped each env (stays once made).  Single GPU only."""
         n, K = int(n_envs), int(accum_steps)
         if n < 1 or K < 1:
             raise ValueError("n_envs >= 1 and accum_steps >= 1")
@@ -449,6 +468,45 @@ class StudentLstmTrainer:
         self._envs_seed = int(seed)
         if self._coin_seed is None:   # the coins follow the envs' seed
             self._set_share(self.teacher_share)
+        if self._noise_seed is None:   # and so does the noise
+            self._set_noise()
+        if actions or self._actions is not None:
+            self._actions = torch.zeros(K, n, 2, **kw)
+            nat.check(self._lib.rdl_envs_bind_actions(self._h, nat.ptr(self._actions), K * n), "rdl_envs_bind_actions")
+
+    # -- action noise in the envs calls ---------------------------------------------------------
+    def set_action_noise(self, mode: str = "none", scale: float = 1.0, seed: int | None = None):
+        """Sample the acting policy in act_envs / rollout_envs / step_envs from the next call on
+        (rdl_envs_set_action_noise; action_noise.py has the modes), under "student" (with the teacher
+        share's coin as it is) and under "teacher" (DART's noisy expert): the action handed to env.step
+        is mean + scale (exp(logstd) | 1) xi of whoever acts at that step, xi a function of (seed,
+        env_base + i, episode, step) alone.  Only that action changes: the records, (c, h), the ring, the
+        windows and the training on every window are as without noise.  ``seed``: the noise's key
+        (default: the envs' seed, whatever attach_envs sets it to).  "none" (the default) is the plain
+        call.  evaluate() never reads this setting.  A captured call keeps the noise it was captured
+        with."""
+        an.native(mode, scale, 0)   # ValueError before anything is kept
+        self._noise, self._noise_seed = (mode, float(scale)), None if seed is None else int(seed)
+        self._set_noise()
+
+    def _set_noise(self):
+        nz = an.native(*self._noise, self._envs_seed if self._noise_seed is None else self._noise_seed)
+        nat.check(self._lib.rdl_envs_set_action_noise(self._h, ctypes.byref(nz)), "rdl_envs_set_action_noise")
+
+    @property
+    def action_noise(self) -> dict:
+        """dict(mode, scale, seed): the handle's setting (rdl_envs_action_noise)"""
+        nz = nat.RdActionNoise()
+        nat.check(self._lib.rdl_envs_action_noise(self._h, ctypes.byref(nz)), "rdl_envs_action_noise")
+        return dict(mode=an.MODE_NAMES[nz.mode], scale=float(nz.scale), seed=int(nz.seed))
+
+    @property
+    def actions(self):
+        """[accum_steps, n, 2] f32, the trainer's own and rewritten by every envs call of either actor:
+        the action that stepped env i at the call's k-th step (the acting mean when the noise is off);
+        rows past a shorter call's ``steps`` keep their old values.  None unless attach_envs(...,
+        actions=True) asked for it."""
+        return self._actions
 
     # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
     def set_teacher_share(self, beta: float, seed: int | None = None):

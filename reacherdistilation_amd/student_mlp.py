@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import action_noise as an
 from .config import OBSPACE_SHAPE, PDFLAT_SHAPE
 from .dist import allreduce_sum_
 from .distill import EvalResult
@@ -61,6 +62,10 @@ nat.register({
     "rdm_envs_set_teacher_share": (INT, [P, F32, U64]),
     "rdm_envs_teacher_share": (F32, [P]),
     "rdm_envs_bind_stepped_with": (INT, [P, P, I64]),
+    "rdm_envs_set_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
+    "rdm_envs_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
+    "rdm_envs_bind_actions": (INT, [P, P, I64]),
+    "rdm_evaluate_noisy": (INT, [P, ctypes.POINTER(RdmEvalConfig), ctypes.POINTER(nat.RdActionNoise), P, P, P]),
     "rdm_set_teacher": (INT, [P, P, P, P]),
     "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
@@ -158,6 +163,7 @@ class StudentMlpTrainer:
         self.teacher = None   # the teacher of evaluate() and of the envs (set_teacher)
         self.n_envs, self.accum_steps, self._envs = 0, 0, None   # attach_envs
         self._envs_seed, self._coin_seed, self._flags = 0, None, None   # set_teacher_share, stepped_with
+        self._noise, self._noise_seed, self._actions = ("none", 1.0), None, None   # set_action_noise, actions
         self._grad = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdm_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdm_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed) if params is None else params)
@@ -225,7 +231,8 @@ class StudentMlpTrainer:
 
     def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
                  first_episode: int = 0, draws=None, final_dist: bool = False, records: bool = False,
-                 grid: int = 0) -> EvalResult:
+                 grid: int = 0, noise: str = "none", noise_scale: float = 1.0,
+                 noise_seed: int | None = None) -> EvalResult:
         """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
         with this student's mean action in ONE launch (rdm_evaluate): the phase-2 loop of
         mlp_train.train(student="mlp") without the optimiser steps.  Per step the teacher set by
@@ -238,7 +245,13 @@ class StudentMlpTrainer:
         tx ty) or, without a table, from Philox(seed, env_base + i, first_episode + e).  Returns a
         distill.EvalResult: returns [E, n]; final_dist [E, n]; records [E, n, 50, 21] in the dataset's
         layout (both pdflats, stepped_with = 1), so that records.view(E * n, 50, 21) goes into
-        DeviceDataset.write_episodes.  Asynchronous on the current stream; no workspace: capturable."""
+        DeviceDataset.write_episodes.  Asynchronous on the current stream; no workspace: capturable.
+        ``noise`` = "policy" or "fixed" (rdm_evaluate_noisy; action_noise.py): the student's action is
+        perturbed, a = mean + noise_scale (exp(logstd) | 1) xi with xi keyed (noise_seed, env_base + i,
+        first_episode + e, step) -- the return under perturbed actions, bitwise the stepwise loop with
+        action_noise.perturb_actions before the step.  ``noise_seed`` defaults to ``seed``.  The envs'
+        set_action_noise is never read here: the default is the noiseless return."""
+        nz = an.native(noise, noise_scale, seed if noise_seed is None else noise_seed)
         n, E = int(n_envs), int(episodes)
         if n < 1 or E < 1:
             raise ValueError("n_envs >= 1 and episodes >= 1")
@@ -257,21 +270,27 @@ class StudentMlpTrainer:
                           first_episode=int(first_episode), grid=int(grid),
                           draws=table.data_ptr() if table is not None else None)
         self._sync_stream()
-        nat.check(self._lib.rdm_evaluate(self._h, ctypes.byref(c), nat.ptr(res.returns),
-                                         nat.ptr(res.final_dist) if final_dist else None,
-                                         nat.ptr(res.records) if records else None), "rdm_evaluate")
+        out = (nat.ptr(res.returns), nat.ptr(res.final_dist) if final_dist else None,
+               nat.ptr(res.records) if records else None)
+        if noise == "none":
+            nat.check(self._lib.rdm_evaluate(self._h, ctypes.byref(c), *out), "rdm_evaluate")
+        else:
+            nat.check(self._lib.rdm_evaluate_noisy(self._h, ctypes.byref(c), ctypes.byref(nz), *out),
+                      "rdm_evaluate_noisy")
         self._keep_eval = table   # the launch reads it asynchronously
         return res
 
     # -- persistent envs: batched on-policy distillation --------------------------------------
     def attach_envs(self, n_envs: int, *, seed: int = 0, env_base: int = 0, grid: int = 0, accum_steps: int = 1,
-                    flags: bool = False):
+                    flags: bool = False, actions: bool = False):
         """Give the trainer ``n_envs`` persistent lockstep envs (rdm_envs_attach; Philox resets keyed
         (seed, env_base + i, episode)) at episode 0, and allocate once the buffers every
         act_envs / rollout_envs / step_envs call fills: ``accum_steps`` = K env steps per call, so K n
         rows per optimiser step.  K = 50 puts all 50 episode phases of the lockstep envs into every
         batch.  Attaching again replaces the envs.  ``flags``: also allocate and bind ``stepped_with``
-        (it is there anyway once a teacher share > 0 is set, and stays once made).  Single GPU only."""
+        (it is there anyway once a teacher share > 0 is set, and stays once made).  ``actions``: also
+        allocate and bind ``actions``, the action that stepped each env (stays once made).  Single GPU
+        only."""
         n, K = int(n_envs), int(accum_steps)
         if n < 1 or K < 1:
             raise ValueError("n_envs >= 1 and accum_steps >= 1")
@@ -291,6 +310,44 @@ class StudentMlpTrainer:
             self._set_share(self.teacher_share)
         if flags or self._flags is not None or self.teacher_share > 0:
             self._bind_flags()
+        if self._noise_seed is None:   # the noise follows the envs' seed
+            self._set_noise()
+        if actions or self._actions is not None:
+            self._actions = torch.zeros(K, n, 2, **kw)
+            nat.check(self._lib.rdm_envs_bind_actions(self._h, nat.ptr(self._actions), K * n), "rdm_envs_bind_actions")
+
+    # -- action noise in the envs calls ---------------------------------------------------------
+    def set_action_noise(self, mode: str = "none", scale: float = 1.0, seed: int | None = None):
+        """Sample the acting policy in act_envs / rollout_envs / step_envs from the next call on
+        (rdm_envs_set_action_noise; action_noise.py has the modes), under "student" (with the teacher
+        share's coin as it is) and under "teacher" (DART's noisy expert): the action handed to env.step
+        is mean + scale (exp(logstd) | 1) xi of whoever acts at that step, xi a function of (seed,
+        env_base + i, episode, step) alone.  Only that action changes: x, both pdflats, stepped_with and
+        the training on every row are as without noise.  ``seed``: the noise's key (default: the envs'
+        seed, whatever attach_envs sets it to).  "none" (the default) is the plain call.  evaluate()
+        never reads this setting.  A captured call keeps the noise it was captured with."""
+        an.native(mode, scale, 0)   # ValueError before anything is kept
+        self._noise, self._noise_seed = (mode, float(scale)), None if seed is None else int(seed)
+        self._set_noise()
+
+    def _set_noise(self):
+        nz = an.native(*self._noise, self._envs_seed if self._noise_seed is None else self._noise_seed)
+        nat.check(self._lib.rdm_envs_set_action_noise(self._h, ctypes.byref(nz)), "rdm_envs_set_action_noise")
+
+    @property
+    def action_noise(self) -> dict:
+        """dict(mode, scale, seed): the handle's setting (rdm_envs_action_noise)"""
+        nz = nat.RdActionNoise()
+        nat.check(self._lib.rdm_envs_action_noise(self._h, ctypes.byref(nz)), "rdm_envs_action_noise")
+        return dict(mode=an.MODE_NAMES[nz.mode], scale=float(nz.scale), seed=int(nz.seed))
+
+    @property
+    def actions(self):
+        """[accum_steps, n, 2] f32, the trainer's own and rewritten by every envs call of either actor:
+        the action that stepped env i at the call's k-th step (the acting mean when the noise is off);
+        rows past a shorter call's ``steps`` keep their old values.  None unless attach_envs(...,
+        actions=True) asked for it."""
+        return self._actions
 
     # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
     def set_teacher_share(self, beta: float, seed: int | None = None):
