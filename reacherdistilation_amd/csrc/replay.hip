@@ -11,15 +11,17 @@
 // contiguous.  The scattered side is the read of the 84-byte records (and the step-major source rows
 // of a push), which runs of 4 to 21 lanes share.  A sample is three launches on the handle's stream:
 // draw (idx[B] into the handle's scratch, and the caller's idx), gather (blockIdx.y picks the output
-// tensor, so each has its own compile-time row width), bump.
+// tensor, so each has its own compile-time row width), bump.  The priority table and the weighted draw
+// are replay_priority.hip's; it launches this file's gathers and bump through replay_internal.h, and a
+// push ends with its launch only while priorities are enabled (push_done).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <new>
 
-#include "../../include/reacher_replay.h"
 #include "rd_common.h"
 #include "rd_physics.h"
+#include "replay_internal.h"
 
 namespace {
 
@@ -30,10 +32,7 @@ constexpr int F_REW = 11, F_T = 12, F_S = 16, F_WITH = 20;
 constexpr int kBlock = 256;
 constexpr int64_t kMaxGrid = 8192;
 
-struct Header {
-    int64_t pushed;
-    int64_t draws;
-};
+using Header = rd::ReplayHeader;
 
 __global__ void replay_bump_kernel(Header* hdr, int64_t pushed, int64_t draws) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -201,16 +200,7 @@ int grid_for(int64_t elements) {
 
 }  // namespace
 
-struct rd_replay {
-    int64_t capacity = 0, max_batch = 0;
-    int64_t host_pushed = 0;   // pushes ISSUED; only to refuse a sample from a ring never pushed to
-    float* ring = nullptr;
-    bool owns_ring = false;
-    Header* hdr = nullptr;
-    int2* scratch = nullptr;   // idx [max_batch]
-    int device = 0;
-    hipStream_t stream = nullptr;
-};
+// struct rd_replay: replay_internal.h (shared with replay_priority.hip)
 
 extern "C" {
 
@@ -255,6 +245,7 @@ int rd_replay_destroy(rd_replay* h) {
     if (h->hdr) (void)hipFree(h->hdr);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->owns_ring && h->ring) (void)hipFree(h->ring);
+    rd::replay_prio_destroy(h);
     delete h;
     return RD_OK;
 }
@@ -309,6 +300,14 @@ static int bump(const char* what, rd_replay* h, int64_t pushed, int64_t draws) {
     return RD_OK;
 }
 
+// the end of every push: with priorities enabled the launch that writes the pushed slots' entries
+// (reacher_replay_priority.h), then the bump
+static int push_done(const char* what, rd_replay* h, int64_t episodes) {
+    if (h->prio.enabled)
+        if (int rc = rd::replay_prio_push_init(what, h, episodes)) return rc;
+    return bump(what, h, episodes, 0);
+}
+
 int rd_replay_push_steps(rd_replay* h, const float* records, int64_t steps, int64_t n_envs) {
     if (!h) return rd::set_error(RD_EINVAL, "rd_replay_push_steps: null handle");
     if (!records) return rd::set_error(RD_EINVAL, "rd_replay_push_steps: null records");
@@ -319,7 +318,7 @@ int rd_replay_push_steps(rd_replay* h, const float* records, int64_t steps, int6
     hipLaunchKernelGGL(replay_push_steps_kernel, dim3(grid_for(E * kSteps * kRec)), dim3(kBlock), 0, h->stream, h->ring,
                        h->hdr, records, E, n_envs, h->capacity);
     RD_HIP(hipGetLastError(), "rd_replay_push_steps: launch");
-    return bump("rd_replay_push_steps: bump launch", h, E, 0);
+    return push_done("rd_replay_push_steps: bump launch", h, E);
 }
 
 int rd_replay_push_episodes(rd_replay* h, const float* records, int64_t episodes) {
@@ -334,7 +333,7 @@ int rd_replay_push_episodes(rd_replay* h, const float* records, int64_t episodes
     hipLaunchKernelGGL(replay_push_episodes_kernel, dim3(grid_for(episodes * kSteps * kRec)), dim3(kBlock), 0, h->stream,
                        h->ring, h->hdr, records, episodes, h->capacity);
     RD_HIP(hipGetLastError(), "rd_replay_push_episodes: launch");
-    return bump("rd_replay_push_episodes: bump launch", h, episodes, 0);
+    return push_done("rd_replay_push_episodes: bump launch", h, episodes);
 }
 
 // rd_replay_push_rows and rd_replay_push_rows_flags, `fn` naming the caller; flags: the latter's
@@ -354,7 +353,7 @@ static int push_rows(const char* fn, rd_replay* h, const float* x, const float* 
     hipLaunchKernelGGL(replay_push_rows_kernel, dim3(grid_for(E * kSteps * kRec)), dim3(kBlock), 0, h->stream, h->ring,
                        h->hdr, x, t_pdflat, s_pdflat, reward, carry, E, n_envs, h->capacity, stepped_with, with_rows);
     RD_HIP(hipGetLastError(), fn);
-    return bump(fn, h, E, 0);
+    return push_done(fn, h, E);
 }
 
 int rd_replay_push_rows(rd_replay* h, const float* x, const float* t_pdflat, const float* s_pdflat, const float* reward,
@@ -407,10 +406,9 @@ int rd_replay_sample_windows(rd_replay* h, const rd_replay_sample* s, float* ob_
     if (int rc = draw("rd_replay_sample_windows: draw launch", h, s, idx, (uint32_t)(kSteps + 1 - s->steps),
                       s->start_mode == RD_REPLAY_START_COMMON))
         return rc;
-    const int64_t ob_elems = (int64_t)s->steps * s->windows * kOb;
-    hipLaunchKernelGGL(replay_gather_windows_kernel, dim3(grid_for(ob_elems), prew_w ? 4 : 3), dim3(kBlock), 0, h->stream,
-                       h->ring, h->scratch, ob_w, prev_w, t_w, prew_w, (uint32_t)s->steps, (uint32_t)s->windows);
-    RD_HIP(hipGetLastError(), "rd_replay_sample_windows: gather launch");
+    if (int rc = rd::replay_gather_windows("rd_replay_sample_windows: gather launch", h, ob_w, prev_w, t_w, prew_w,
+                                           s->steps, s->windows))
+        return rc;
     return bump("rd_replay_sample_windows: bump launch", h, 0, 1);
 }
 
@@ -424,10 +422,31 @@ int rd_replay_sample_rows(rd_replay* h, const rd_replay_sample* s, float* x, flo
     rd::DeviceGuard g(h->device);
     RD_HIP(g.err, "rd_replay_sample_rows: hipSetDevice");
     if (int rc = draw("rd_replay_sample_rows: draw launch", h, s, idx, (uint32_t)kSteps, 0)) return rc;
-    hipLaunchKernelGGL(replay_gather_rows_kernel, dim3(grid_for(s->windows * 4), 2), dim3(kBlock), 0, h->stream, h->ring,
-                       h->scratch, x, t_pdflat, (uint32_t)s->windows);
-    RD_HIP(hipGetLastError(), "rd_replay_sample_rows: gather launch");
+    if (int rc = rd::replay_gather_rows("rd_replay_sample_rows: gather launch", h, x, t_pdflat, s->windows)) return rc;
     return bump("rd_replay_sample_rows: bump launch", h, 0, 1);
 }
 
 }  // extern "C"
+
+// what replay_priority.hip launches of this file's kernels (replay_internal.h)
+namespace rd {
+
+int replay_gather_rows(const char* what, rd_replay* h, float* x, float* t_pdflat, int64_t rows) {
+    hipLaunchKernelGGL(replay_gather_rows_kernel, dim3(grid_for(rows * 4), 2), dim3(kBlock), 0, h->stream, h->ring,
+                       h->scratch, x, t_pdflat, (uint32_t)rows);
+    RD_HIP(hipGetLastError(), what);
+    return RD_OK;
+}
+
+int replay_gather_windows(const char* what, rd_replay* h, float* ob_w, float* prev_w, float* t_w, float* prew_w,
+                          int32_t steps, int64_t windows) {
+    const int64_t ob_elems = (int64_t)steps * windows * kOb;
+    hipLaunchKernelGGL(replay_gather_windows_kernel, dim3(grid_for(ob_elems), prew_w ? 4 : 3), dim3(kBlock), 0, h->stream,
+                       h->ring, h->scratch, ob_w, prev_w, t_w, prew_w, (uint32_t)steps, (uint32_t)windows);
+    RD_HIP(hipGetLastError(), what);
+    return RD_OK;
+}
+
+int replay_bump(const char* what, rd_replay* h, int64_t pushed, int64_t draws) { return bump(what, h, pushed, draws); }
+
+}  // namespace rd

@@ -118,7 +118,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32",
-               beta0: float = 0.0, beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0):
+               beta0: float = 0.0, beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0,
+               replay_priority: str = "none"):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -159,7 +160,14 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     ``noise``, ``noise_scale``: action noise in every envs call of the run, warm-up steps included
     (StudentLstmTrainer.set_action_noise, keyed by ``seed``): "fixed" with the teacher acting
     (warmup_steps = opt_steps) is DART's noisy expert, "policy" samples whoever acts.  The evaluations
-    stay noiseless.  The default "none" is the same launches as before."""
+    stay noiseless.  The default "none" is the same launches as before.
+    ``replay_priority`` (needs a ring): "record" draws the batches in proportion to the records' priorities
+    (ReplayRing.enable_priorities: the student's squared action error against the teacher) instead of
+    uniformly; a push writes the priorities from the record's own s_pdflat, the student as it acted, or
+    the maximum priority when the teacher stepped the act call (s_pdflat is zero there and says nothing
+    about the student).  "refresh" also re-scores every sampled batch with the current student (one
+    forward per optimiser step, ReplayRing.update_priorities) before it trains on it.  The default
+    "none" is the uniform loop, the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K, T = int(n_envs), int(opt_steps), int(accum_steps), STEPS_UNROLLED
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
@@ -169,6 +177,9 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     if n < 1 or K < 50 or K % 50:
         raise ValueError("n_envs >= 1 and accum_steps a positive multiple of 50")
     cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
+    prio = str(replay_priority)
+    if prio not in ("none", "record", "refresh") or (prio != "none" and cap <= 0):
+        raise ValueError('replay_priority is "none", "record" or "refresh", and needs replay_capacity > 0')
     if cap < 0 or (cap and (Bw < 1 or upa < 1 or int(replay_recent) < 0 or n * (K // 50) > cap)):
         raise ValueError("replay_capacity >= (accum_steps / 50) n_envs, replay_windows >= 1, updates_per_act >= 1 "
                          "and replay_recent >= 0")
@@ -185,6 +196,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     if cap:
         from .replay import ReplayRing
         ring = st.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
+        if prio != "none":
+            ring.enable_priorities(init="record")
     for k in range(steps):
         act_with = "teacher" if k < int(warmup_steps) else "student"
         if beta0 > 0 and act_with == "student" and (ring is None or k % upa == 0):
@@ -195,9 +208,17 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
         else:
             if k % upa == 0:
                 r = st.act_envs(act_with)
+                if prio != "none":
+                    ring.set_priority_init("const" if act_with == "teacher" else "record")
                 ring.push_steps(r.records)
                 mean_reward = r.reward.mean()
-            ob_w, prev_w, t_w, _ = ring.sample_windows(T, Bw, recent=int(replay_recent))
+            if prio == "none":
+                ob_w, prev_w, t_w, _ = ring.sample_windows(T, Bw, recent=int(replay_recent))
+            else:
+                ob_w, prev_w, t_w, _, idx = ring.sample_windows(T, Bw, recent=int(replay_recent), with_idx=True,
+                                                                prioritized=True)
+                if prio == "refresh":
+                    ring.update_priorities(idx, st.forward(ob_w, prev_w)[0])
             st.step(ob_w, prev_w, t_w)
             rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:

@@ -121,7 +121,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                accum_steps: int = 50, warmup_steps: int = 0, seed: int = 0, teacher=None, device="cuda:0",
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, beta0: float = 0.0,
-               beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0):
+               beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0,
+               replay_priority: str = "none"):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -153,7 +154,14 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     ``noise``, ``noise_scale``: action noise in every envs call of the run, warm-up steps included
     (StudentMlpTrainer.set_action_noise, keyed by ``seed``): "fixed" with the teacher acting
     (warmup_steps = opt_steps) is DART's noisy expert, "policy" samples whoever acts.  The evaluations
-    stay noiseless.  The default "none" is the same launches as before."""
+    stay noiseless.  The default "none" is the same launches as before.
+    ``replay_priority`` (needs a ring): "record" draws the batches in proportion to the records' priorities
+    (ReplayRing.enable_priorities: the student's squared action error against the teacher) instead of
+    uniformly; a push writes the priorities from the record's own s_pdflat, the student as it acted, or
+    the maximum priority when the teacher stepped the act call (s_pdflat is zero there and says nothing
+    about the student).  "refresh" also re-scores every sampled batch with the current student (one
+    forward per optimiser step, ReplayRing.update_priorities) before it trains on it.  The default
+    "none" is the uniform loop, the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
@@ -161,6 +169,9 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     if not 0.0 <= float(beta0) <= 1.0 or not 0.0 <= float(beta_decay) <= 1.0:
         raise ValueError("beta0 and beta_decay in [0, 1]")
     cap, Bw, upa = int(replay_capacity), int(replay_windows), int(updates_per_act)
+    prio = str(replay_priority)
+    if prio not in ("none", "record", "refresh") or (prio != "none" and cap <= 0):
+        raise ValueError('replay_priority is "none", "record" or "refresh", and needs replay_capacity > 0')
     if cap < 0 or (cap and (Bw < 1 or upa < 1 or int(replay_recent) < 0 or K < 50 or K % 50 or n * (K // 50) > cap)):
         raise ValueError("with a replay ring: accum_steps a positive multiple of 50, replay_capacity >= "
                          "(accum_steps / 50) n_envs, replay_windows >= 1, updates_per_act >= 1, replay_recent >= 0")
@@ -176,6 +187,8 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     if cap:
         from .replay import ReplayRing
         ring = sm.replay = ReplayRing(cap, device=device, seed=seed, max_batch=Bw)
+        if prio != "none":
+            ring.enable_priorities(init="record")
     for k in range(steps):
         act_with = "teacher" if k < int(warmup_steps) else "student"
         if beta0 > 0 and act_with == "student" and (ring is None or k % upa == 0):
@@ -186,10 +199,18 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
         else:
             if k % upa == 0:
                 r = sm.act_envs(act_with)
+                if prio != "none":
+                    ring.set_priority_init("const" if act_with == "teacher" else "record")
                 ring.push_rows(r, stepped_with=float(act_with == "student") if sm.stepped_with is None
                                else sm.stepped_with)
                 mean_reward = r.reward.mean()
-            sm.step(*ring.sample_rows(Bw, recent=int(replay_recent)))
+            if prio == "none":
+                sm.step(*ring.sample_rows(Bw, recent=int(replay_recent)))
+            else:
+                x, t, idx = ring.sample_rows(Bw, recent=int(replay_recent), with_idx=True, prioritized=True)
+                if prio == "refresh":
+                    ring.update_priorities(idx, sm.forward(x))
+                sm.step(x, t)
             rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:
             evals.append((k + 1, float(sm.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
