@@ -69,6 +69,13 @@ typedef struct {
                                 helper-pair layout for a batch of at most two 16-env groups
                                 per CU (pairs 2, 3 of a workgroup run the teacher forwards
                                 of pairs 0, 1); a fixed size never does      */
+    int32_t teacher_tiles;   /* which of a group's 16-env tiles take their teacher forward from
+                                the pair's consumer wave (bit t = tile t): -1 = the
+                                library's default (2: tile 1), 0 = none, 2 | 10 | 14 (0b0010, 0b1010,
+                                0b1110) as built.  Used by the f32 student with f32_split at
+                                K = 1 (env and observation-batch launches); the bf16 student's
+                                kernel is 0b1010 whatever this says.  Same arithmetic per net:
+                                the results do not depend on it.  Any other value: RD_EINVAL  */
 } rdd_config;
 
 /* Student precision.  RDD_DTYPE_F32: every product exact f32 (v_mfma_f32_16x16x4_f32).
@@ -233,10 +240,11 @@ int rdd_get_counters(rdd_trainer* tr, int64_t* env_steps, int64_t* opt_steps);
 int rdd_read_metrics(rdd_trainer* tr, int64_t count, double* out);
 /* The layout launch_rollout chose for the trainer's last rollout launch (env, obs or rows):
  * out[0] = envs/rows per group (16|32|64), out[1] = workgroups, out[2] = 1 if the helper-pair
- * kernel ran, out[3] = 0 env / 1 obs / 2 rows.  Host-only, no device call, no sync.  Before the
- * first launch: the env rollout's group size and grid, out[2] = out[3] = 0.
- * RD_EINVAL: NULL trainer or out. */
-int rdd_last_layout(const rdd_trainer* tr, int32_t out[4]);
+ * kernel ran, out[3] = 0 env / 1 obs / 2 rows, out[4] = the teacher_tiles mask of the kernel that
+ * ran (0 where the producer wave ran every teacher forward, or none ran).  Host-only, no device
+ * call, no sync.  Before the first launch: the env rollout's group size and grid, out[2] = out[3]
+ * = out[4] = 0.  RD_EINVAL: NULL trainer or out. */
+int rdd_last_layout(const rdd_trainer* tr, int32_t out[5]);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,8 @@ struct rdd_trainer {
     unsigned long long* dbg = nullptr;   // RD_STAMPS builds only
     int last_grid = 0;                   // workgroups of the last rollout (rows of ws to reduce)
     int last_gs = GROUP, last_hlp = 0, last_mode = 0;   // ... its group size, helper layout, 0 env / 1 obs / 2 rows
+    int last_tcm = 0;                    // ... and the tiles whose teacher forward the consumer wave ran (mask)
+    int tcm = 0;                         // that mask for the f32-split student's K = 1 launches (cfg.teacher_tiles)
     int ws_rows = 0;                     // rows of ws (the device's CU count, or cfg.grid)
     int cus = 0;                         // the device's CU count (rdd_evaluate's grid: no query per launch)
     int gs = GROUP;                      // envs per group of the env rollout
@@ -139,6 +141,16 @@ int grid_for(int64_t n, int gs, int cap) {
     const int64_t want = ((n + gs - 1) / gs + PAIRS - 1) / PAIRS;   // one group per pair at least
     return (int)(want < cap ? want : cap);
 }
+
+// Which tiles of a group take their teacher forward from the consumer wave (rollout_kernel's TCM;
+// DESIGN.md §3 "Where a pair's time goes").  The bf16 student's kernel is built with 0b1010 only.
+// The f32-split student's K = 1 teacher-mode kernel exists with none, one, two or three of a
+// group's four tiles moved; rdd_config.teacher_tiles picks one, -1 the default below.  Tile 1 alone
+// is the fastest at every batch size and group size measured (c4 -1.4 us per step, c3 -0.6): the
+// consumer runs it while it would wait for the group's first tile; with two or three tiles moved
+// the consumer ends last (profiles/r07_teacher_tiles_ab.txt).
+constexpr int kTeacherTilesDefault = 0b0010;
+bool teacher_tiles_ok(int m) { return m == -1 || m == 0 || m == 0b0010 || m == 0b1010 || m == 0b1110; }
 
 ReduceArgs reduce_args(const rdd_trainer* t, int reduce, int adam, int accum) {
     ReduceArgs a;
@@ -206,11 +218,18 @@ int launch_rollout(rdd_trainer* t, const float* obs_in = nullptr, int64_t n_obs 
     t->last_gs = a.gs;
     t->last_hlp = hlp;
     t->last_mode = tflat_in ? 2 : (obs_in ? 1 : 0);
+    // the f32-split student's plain K = 1 teacher-mode launch (env or obs): the instance of the trainer's mask
+    const int tcm = !bs && spl && !hlp && !tflat_in && ksteps == 1 ? t->tcm : 0;
+    t->last_tcm = bs && spl && !tflat_in && ksteps == 1 ? 0b1010 : tcm;
     void (*k)(RolloutArgs) =
-        bs ? (spl ? rollout_kernel<true, true, true, MD_TEACHER, false, true>   // TC: DESIGN.md §3 "c5"
+        bs ? (spl ? rollout_kernel<true, true, true, MD_TEACHER, false, 0b1010>   // DESIGN.md §3 "c5"
                   : rollout_kernel<true, false, true, MD_TEACHER>)
            : hlp ? (spl ? rollout_kernel<false, true, false, MD_HELPER> : rollout_kernel<false, false, false, MD_HELPER>)
-                 : (spl ? rollout_kernel<false, true, false, MD_TEACHER> : rollout_kernel<false, false, false, MD_TEACHER>);
+                 : (spl ? (tcm == 0b1110   ? rollout_kernel<false, true, false, MD_TEACHER, false, 0b1110>
+                           : tcm == 0b1010 ? rollout_kernel<false, true, false, MD_TEACHER, false, 0b1010>
+                           : tcm == 0b0010 ? rollout_kernel<false, true, false, MD_TEACHER, false, 0b0010>
+                                           : rollout_kernel<false, true, false, MD_TEACHER>)
+                        : rollout_kernel<false, false, false, MD_TEACHER>);
     if (ksteps > 1)   // K steps per launch: the producer steps the envs it reads (no CP)
         k = bs ? (spl ? rollout_kernel<true, true, false, MD_TEACHER, true> : rollout_kernel<true, false, false, MD_TEACHER, true>)
                : (spl ? rollout_kernel<false, true, false, MD_TEACHER, true> : rollout_kernel<false, false, false, MD_TEACHER, true>);
@@ -253,6 +272,9 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
         (cfg->f32_split != 0 && cfg->f32_split != 1) ||
         (cfg->group_envs != 0 && cfg->group_envs != 16 && cfg->group_envs != 32 && cfg->group_envs != 64))
         return rd::set_error(RD_EINVAL, "rdd_create: bad config");
+    if (!teacher_tiles_ok(cfg->teacher_tiles))
+        return rd::set_error(RD_EINVAL, "rdd_create: teacher_tiles %d is not built (-1 default, 0, 2 = 0b0010, "
+                                        "10 = 0b1010, 14 = 0b1110)", (int)cfg->teacher_tiles);
     rd::DeviceGuard g(device);
     RD_HIP(g.err, "rdd_create: hipSetDevice");
     rdd_trainer* t = new (std::nothrow) rdd_trainer();
@@ -269,6 +291,7 @@ int rdd_create(rdd_trainer** out, const rdd_config* cfg, int device, void* hip_s
     t->grid = grid_for(cfg->n_envs, t->gs, cap);
     t->last_grid = t->grid;
     t->last_gs = t->gs;
+    t->tcm = cfg->teacher_tiles < 0 ? kTeacherTilesDefault : cfg->teacher_tiles;
     const size_t netf = P_TOT + 2 * OBD;
     rd::DeviceAllocs& mem = t->mem;
     mem.stream = t->stream;
@@ -603,12 +626,13 @@ int rdd_read_metrics(rdd_trainer* t, int64_t count, double* out) {
     return rd::read_ring("rdd_read_metrics", "steps", t->hist, t->cfg.metrics_len, N_MET, steps, count, out);
 }
 
-int rdd_last_layout(const rdd_trainer* t, int32_t out[4]) {
+int rdd_last_layout(const rdd_trainer* t, int32_t out[5]) {
     if (!t || !out) return rd::set_error(RD_EINVAL, "rdd_last_layout: null argument");
     out[0] = t->last_gs;
     out[1] = t->last_grid;
     out[2] = t->last_hlp;
     out[3] = t->last_mode;
+    out[4] = t->last_tcm;
     return RD_OK;
 }
 

@@ -36,6 +36,22 @@ __device__ __forceinline__ bool wait_ge(const uint32_t* f, uint32_t target, uint
     }
 }
 
+// wait_ge whose exit the compiler sees as wave-uniform (every lane reads the same counter, so the
+// first lane's value is the wave's).  The f32 student's teacher hand-off waits use it: around a
+// divergent exit the compiler keeps a second copy of every accumulator that is live across the wait,
+// and the f32-split consumer (82 of them) then spills.
+__device__ __forceinline__ bool wait_ge_uniform(const uint32_t* f, uint32_t target, uint32_t* err) {
+    for (uint32_t spins = 0;; ++spins) {
+        const uint32_t v = __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (__builtin_amdgcn_readfirstlane(v) >= target) return true;
+        if (spins > SPIN_LIMIT) {
+            if ((threadIdx.x & 63) == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return false;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+}
+
 __device__ __forceinline__ void publish(uint32_t* f, uint32_t v) {
     __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -71,15 +87,25 @@ __device__ __forceinline__ float env_step_group(const RolloutArgs& a, uint32_t C
 constexpr int MD_TEACHER = 0, MD_ROWS = 1, MD_HELPER = 2;
 // KS: a.ksteps env steps in one launch (rdd_step_accum); the K = 1 instances are compiled without
 // the step loop.
-// TC (bf16 student with the split teacher, config 5): the consumer wave runs the teacher forward
-// of each group's odd tiles from the producer's observation rows and hands the means back
-// (P_TM, flag [3]); the producer publishes each group's observations (flag [2]) and runs the
-// teacher of the even tiles beside the student forwards (c5 -0.5 us per step).
-template <bool BS, bool SPL, bool CP, int MD, bool KS = false, bool TC = false>
+// TCM (split teacher, K = 1; rdd_config.teacher_tiles): bit t set = the consumer wave runs the
+// teacher forward of tile t of every group from the producer's observation rows and hands the
+// means back (P_TM, flag [3]); the producer publishes each group's observations (flag [2]) and
+// runs the teacher of the other tiles beside the student forwards.  Tile 0 is never the
+// consumer's: it needs the group's observations published first.  0: every teacher forward on
+// the producer.  0b1010 is config 5's layout (bf16 student, c5 -0.5 us per step).
+template <bool BS, bool SPL, bool CP, int MD, bool KS = false, int TCM = 0>
 __global__ __launch_bounds__(BLOCK, 2) void rollout_kernel(RolloutArgs a) {
     constexpr bool TGT = MD == MD_ROWS, HLP = MD == MD_HELPER;
-    static_assert(!TC || (BS && MD == MD_TEACHER && !KS), "teacher on the consumer: bf16 student, K = 1");
-    constexpr int P_TM = CP ? P_ACT : P_SACT;   // TC: the consumer's teacher means of one tile [16][2]
+    constexpr bool TC = TCM != 0;
+    static_assert(TCM == 0 || (MD == MD_TEACHER && !KS && SPL), "teacher on the consumer: split teacher, K = 1");
+    static_assert((TCM & ~((1 << GROUP / TILE) - 2)) == 0, "a mask over tiles 1 .. 3; tile 0 stays on the producer");
+    // is tile t (t + 1: tn) the consumer's?  0b1010 keeps the odd-tile test config 5 was tuned with
+    // (the same tiles for t < 4, and that instance's ISA)
+    auto tc_tile = [](int t) { return TCM == 0b1010 ? (t & 1) != 0 : ((TCM >> t) & 1) != 0; };
+    auto tc_next = [](int t) { return TCM == 0b1010 ? !(t & 1) : ((TCM >> (t + 1)) & 1) != 0; };
+    // TC: the consumer's teacher means of one tile [16][2].  !CP: P_SACT carries actions only in the
+    // consumer-side-step kernels (the CP store below), so it is free here
+    constexpr int P_TM = CP ? P_ACT : P_SACT;
     static_assert(!HLP || !BS, "helper pairs: f32 student kernels only");
     constexpr int TN = TGT ? 0 : img_t(SPL), SN = img_s(BS, SPL);
     __shared__ __attribute__((aligned(16))) float lds[TN + SN + PAIRS * PSCR];
@@ -277,7 +303,7 @@ __global__ __launch_bounds__(BLOCK, 2) void rollout_kernel(RolloutArgs a) {
                         else mlp_forward_pair<true>(LT, LS, obt, j, g, H1, H2, mt0, mt1, ms0, ms1);
                     }
                 } else if constexpr (BS) {
-                    if (TC && (t & 1)) {   // the consumer ran this tile's teacher forward
+                    if (TC && tc_tile(t)) {   // the consumer ran this tile's teacher forward
                         mlp_forward_bf16(LS, obt, j, g, H1, H2, ms0, ms1);
                         if (!(ok = wait_ge(flags + 3, ++tct, err))) break;
                         mt0 = PS[P_TM + 2 * j];
@@ -296,8 +322,18 @@ __global__ __launch_bounds__(BLOCK, 2) void rollout_kernel(RolloutArgs a) {
                     // hygiene test re-checks the built ISA -- at 3 % of the kernel, where fencing all
                     // 16 cost 16 % (c4 exact 110.1 / 113.8 / 128.0 us per step unfenced / kPairFence /
                     // every step, profiles/r06a_*, r06b_*)
-                    if constexpr (SPL) mlp_forward_pair_split(LT, LS, obt, j, g, H1, H2, mt0, mt1, ms0, ms1);
-                    else mlp_forward_pair<false, kPairFence>(LT, LS, obt, j, g, H1, H2, mt0, mt1, ms0, ms1);
+                    if constexpr (SPL) {
+                        if (TC && tc_tile(t)) {   // as the bf16 student's: the student alone, the means from P_TM
+                            mlp_forward_split_t<true>(LS, obt, j, g, H1, H2, ms0, ms1);
+                            if (!(ok = wait_ge_uniform(flags + 3, ++tct, err))) break;
+                            mt0 = PS[P_TM + 2 * j];
+                            mt1 = PS[P_TM + 2 * j + 1];
+                        } else {
+                            mlp_forward_pair_split(LT, LS, obt, j, g, H1, H2, mt0, mt1, ms0, ms1);
+                        }
+                    } else {
+                        mlp_forward_pair<false, kPairFence>(LT, LS, obt, j, g, H1, H2, mt0, mt1, ms0, ms1);
+                    }
                 }
                 STAMP(12);
                 // loss
@@ -713,21 +749,33 @@ __global__ __launch_bounds__(BLOCK, 2) void rollout_kernel(RolloutArgs a) {
             const uint32_t base = grp * (uint32_t)gs;
             const int ntile = (int)min((uint32_t)(gs / TILE), (n32 - base + TILE - 1) / TILE);
             if constexpr (TC) {
-                if (!(ok = wait_ge(flags + 2, gi + 1, err))) break;
+                if (!(ok = BS ? wait_ge(flags + 2, gi + 1, err) : wait_ge_uniform(flags + 2, gi + 1, err))) break;
             }
             for (int t = 0; ok && t < ntile; ++t) {
                 if constexpr (TC) {
-                    // the teacher forward of the next (odd) tile, from the producer's observation rows:
-                    // its means go to P_TM, read by the producer at that tile (one tile in flight: the
-                    // producer takes them before it publishes the tile this wave consumes next)
-                    if (!(t & 1) && t + 1 < ntile) {
+                    // the teacher forward of tile t + 1, if it is this wave's, from the producer's observation
+                    // rows, before the backward of tile t: its means go to P_TM (a single buffer: one tile
+                    // in flight), read by the producer at tile t + 1 before it publishes that tile.
+                    // Order (no deadlock, no overwrite).  The producer publishes tile u after: its own
+                    // forward of u; flag [3] of u if u is masked; the slot of u - 1 freed.  This wave frees
+                    // the slot of u - 1 in bwd_tile(u - 1) and publishes flag [3] of u before bwd_tile(u - 1),
+                    // both without waiting for anything past tile u - 1's publication, so by induction
+                    // every tile gets published.  P_TM of u may be overwritten only once the producer has
+                    // read it, i.e. once tile u is published.  When this wave writes the means of t + 1 it
+                    // has passed bwd_tile(t - 1), so tiles <= t - 1 are published: a masked tile <= t - 1
+                    // (0b1010, 0b0010, and the previous group's tiles) has been read.  Only when tile t is
+                    // masked too (0b1110: t = 1, 2) may its means still be unread: there the forward runs
+                    // first, into registers, and the store waits for tile t's publication -- the same
+                    // flag bwd_tile(t) waits for next, which the producer raises without needing the
+                    // means of t + 1.
+                    if (tc_next(t) && t + 1 < ntile) {
                         const float* obt = PS + P_SO + TILE * (t + 1) * SOS;
                         float m0, m1;
-                        if constexpr (SPL) {
-                            mlp_forward_split(LT, obt, j, g, m0, m1);
-                        } else {
-                            f32x4 h1[4], h2[4];
-                            mlp_forward<true>(LT, obt, j, g, h1, h2, m0, m1);
+                        STAMP(18);   // (the helper layout's stamp slots: MD_HELPER never runs with a mask)
+                        mlp_forward_split(LT, obt, j, g, m0, m1);
+                        STAMP(19);
+                        if constexpr ((TCM & (TCM >> 1)) != 0) {
+                            if (tc_tile(t) && !(ok = wait_ge_uniform(flags, tiles + 1, err))) break;
                         }
                         if (g == 0) {
                             PS[P_TM + 2 * j] = m0;

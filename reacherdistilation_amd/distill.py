@@ -35,7 +35,8 @@ class RddConfig(ctypes.Structure):
     _fields_ = [("n_envs", I64), ("n_envs_global", I64), ("env_base", I64), ("seed", U64),
                 ("loss", I32), ("act_with", I32), ("lr", F32), ("beta1", F32), ("beta2", F32),
                 ("eps", F32), ("grid", I32), ("metrics_len", I32), ("stagger", I32),
-                ("student_dtype", I32), ("accum_steps", I32), ("f32_split", I32), ("group_envs", I32)]
+                ("student_dtype", I32), ("accum_steps", I32), ("f32_split", I32), ("group_envs", I32),
+                ("teacher_tiles", I32)]
 
 
 class RddEvalConfig(ctypes.Structure):
@@ -107,6 +108,8 @@ class DistillConfig:
     f32_split: bool = True             # f32 hidden layers on bf16 MFMAs via exact 3-piece splits (reacher_distill.h);
     #                                    False: every product on the f32 MFMA (same tolerances, ~20 % slower)
     group_envs: int = 0                # envs per rollout group: 0 = auto, 16 | 32 | 64 fixed (summation order only)
+    teacher_tiles: int = -1            # tiles of a group whose teacher forward the consumer wave runs (f32 student,
+    #                                    f32_split, K = 1): -1 = library default, 0 = none, 0b0010 | 0b1010 | 0b1110
 
 
 class DistillTrainer:
@@ -134,7 +137,7 @@ class DistillTrainer:
                       beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.eps, grid=cfg.grid, metrics_len=cfg.metrics_len,
                       stagger=int(bool(cfg.stagger)), student_dtype=DTYPES[cfg.student_dtype],
                       accum_steps=max(1, int(cfg.accum_steps)), f32_split=int(bool(cfg.f32_split)),
-                      group_envs=int(cfg.group_envs))
+                      group_envs=int(cfg.group_envs), teacher_tiles=int(cfg.teacher_tiles))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             nat.check(self._lib.rdd_create(ctypes.byref(h), ctypes.byref(c), self.device.index or 0,
@@ -297,12 +300,14 @@ class DistillTrainer:
         nat.check(self._lib.rdd_get_counters(self._h, ctypes.byref(e), ctypes.byref(o)), "rdd_get_counters")
         return e.value, o.value
 
-    def last_layout(self):
+    def last_layout(self, teacher_tiles: bool = False):
         """(rows per group, workgroups, helper-pair kernel, mode) of the last rollout launch
-        (rdd_last_layout); mode is "env", "obs" or "rows".  Host-only."""
-        out = (I32 * 4)()
+        (rdd_last_layout); mode is "env", "obs" or "rows".  teacher_tiles: a fifth entry, the mask
+        of the tiles whose teacher forward the consumer wave ran.  Host-only."""
+        out = (I32 * 5)()
         nat.check(self._lib.rdd_last_layout(self._h, out), "rdd_last_layout")
-        return out[0], out[1], bool(out[2]), ("env", "obs", "rows")[out[3]]
+        lay = out[0], out[1], bool(out[2]), ("env", "obs", "rows")[out[3]]
+        return lay + (out[4],) if teacher_tiles else lay
 
     def set_stream(self, stream: torch.cuda.Stream):
         nat.check(self._lib.rdd_set_stream(self._h, ctypes.c_void_p(stream.cuda_stream)), "rdd_set_stream")

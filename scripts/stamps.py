@@ -25,7 +25,8 @@ def main():
     # RD_SPLIT=1: f32_split; RD_WL=c5: DAgger with the bf16 student
     c5 = os.environ.get("RD_WL") == "c5"
     tr = DistillTrainer(DistillConfig(n_envs=n, seed=0, f32_split=os.environ.get("RD_SPLIT") == "1",
-                                      act_with="student" if c5 else "teacher", student_dtype="bf16" if c5 else "f32"),
+                                      act_with="student" if c5 else "teacher", student_dtype="bf16" if c5 else "f32",
+                                      teacher_tiles=int(os.environ.get("RD_TT", "-1"))),   # RD_TT: rdd_config.teacher_tiles
                         device="cuda:0")
     lib = nat.load()
     lib.rdd_debug_stamps.restype = ctypes.c_int
@@ -78,6 +79,10 @@ def main():
         "consumer_slot_read": d(3, 13, cons),
         "consumer_dw2_dh1": d(13, 14, cons),
         "consumer_dz1_dw1": d(14, 15, cons),
+        # teacher_tiles: the consumer's teacher forwards (stamps 18 -> 19, the helper layout's slots)
+        "consumer_teacher_fwd": None if owners else d(18, 19, cons),
+        "teacher_tiles": tr.last_layout(teacher_tiles=True)[4],
+        "producer_loop_end": d(0, 6, prod), "consumer_loop_end": d(0, 6, cons),
         "helper_teacher_start": d(0, 18, hp) if owners else None,
         "helper_teacher_fwd": d(18, 19, hp) if owners else None,
         "helper_env_step": d(19, 23, hp) if owners else None,
