@@ -67,6 +67,7 @@
 
 #include "reacher.h"
 #include "reacher_action_noise.h"   /* rd_action_noise: rdl_envs_set_action_noise, rdl_evaluate_noisy */
+#include "reacher_obs_faults.h"     /* rd_obs_faults: rdl_envs_set_obs_faults, rdl_evaluate_faulty */
 
 #ifdef __cplusplus
 extern "C" {
@@ -350,6 +351,39 @@ int rdl_envs_bind_actions(rdl_trainer* t, float* buf /*[K][n][2] step-major*/, i
  * (call rdl_evaluate). */
 int rdl_evaluate_noisy(rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
                        float* returns, float* final_dist, float* records, float* state_out);
+
+/* Sensor faults on what the student reads in the envs calls above (reacher_obs_faults.h has the
+ * definition): the handle has an rd_obs_faults; the default mode = RD_OBS_CLEAN, and a set back to it,
+ * leaves every call exactly as described above (the same launch of the same kernel).  Otherwise, in
+ * rdl_envs_act / rdl_rollout_envs / rdl_step_envs under RDL_ACT_STUDENT, the student's query reads
+ * every record of its window masked: record j of the open episode carries the mask of (e = env_base +
+ * i, episode, j) at every position and in every later query that still holds it -- a reading once lost
+ * stays lost -- whichever call recorded it (a teacher call's records and those of an earlier call are
+ * masked the same: the mask is a pure function and the handle's history keeps the clean readings).
+ * Zero-padding records stay zero and prev is untouched.  ONLY S_s, and through it (c, h) and the
+ * trajectory, changes: the teacher reads the clean ob, and the records' layout, the windows (ob_w,
+ * prev_w, t_w hold the clean readings), stepped_with, reward, actions and the training on every window
+ * with its own keep_prob dropout are as without faults.  They compose with the beta-coin and the
+ * action noise.  RDL_ACT_TEACHER calls evaluate no student: they ignore the setting and launch what
+ * they launch without it.  The mask does not depend on the grid or the split of the steps over calls;
+ * a captured call replays the NEXT steps' mask and keeps the mode, keep_prob and seed it was captured
+ * with.  rdl_envs_set_obs_faults is host-only, like rdl_envs_set_action_noise; it may precede
+ * rdl_envs_attach and survives attach and reset.  rdl_evaluate never reads it.  RD_EINVAL, naming the
+ * function and the field, before the handle is read: NULL struct; unknown mode; keep_prob NaN, <= 0 or
+ * > 1; then a NULL trainer.
+ * rdl_envs_obs_faults copies the setting to *out (RD_EINVAL for a NULL trainer or out). */
+int rdl_envs_set_obs_faults(rdl_trainer* t, const rd_obs_faults* of);
+int rdl_envs_obs_faults(const rdl_trainer* t, rd_obs_faults* out);
+
+/* rdl_evaluate with the student reading its windows through *of (RD_OBS_DROPOUT or RD_OBS_MISSING) at
+ * Philox episode first_episode + e, with or without a draws table, and, with nz, its action perturbed
+ * as rdl_evaluate_noisy perturbs it (nz = NULL or mode RD_NOISE_NONE: the mean acts): the records
+ * (clean ob), returns, final_dist and state_out of that trajectory.  Bitwise the stepwise loop with
+ * rd_mask_obs on every record as it enters the window.  Independent of the envs' settings; capturable.
+ * RD_EINVAL as rdl_evaluate, and before it: NULL of, unknown mode, a bad keep_prob, mode =
+ * RD_OBS_CLEAN (call the plain function); a bad *nz as rdl_evaluate_noisy names it. */
+int rdl_evaluate_faulty(rdl_trainer* t, const rdl_eval_config* cfg, const rd_obs_faults* of, const rd_action_noise* nz,
+                        const float* state0, float* returns, float* final_dist, float* records, float* state_out);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@
 
 #include "reacher.h"
 #include "reacher_action_noise.h"   /* rd_action_noise: rdm_envs_set_action_noise, rdm_evaluate_noisy */
+#include "reacher_obs_faults.h"     /* rd_obs_faults: rdm_envs_set_obs_faults, rdm_evaluate_faulty */
 #include "reacher_replay.h"   /* rd_replay: rd_replay_push_rows_flags, below */
 
 #ifdef __cplusplus
@@ -271,6 +272,38 @@ int rdm_envs_bind_actions(rdm_trainer* t, float* buf /*[K][n][2] step-major*/, i
  * (call rdm_evaluate). */
 int rdm_evaluate_noisy(rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz,
                        float* returns, float* final_dist, float* records);
+
+/* Sensor faults on what the student reads in the envs calls above (reacher_obs_faults.h has the
+ * definition): the handle has an rd_obs_faults; the default mode = RD_OBS_CLEAN, and a set back to it,
+ * leaves every call exactly as described above (the same launch of the same kernel).  Otherwise, in
+ * rdm_envs_act / rdm_rollout_envs / rdm_step_envs under RDM_ACT_STUDENT, the student's forward reads
+ * ob masked at e = env_base + i and the env's device clock (episode, s) in place of ob; prev_pdflat and
+ * prev_rew of its row are untouched.  ONLY S_s, and through it the trajectory, changes: the teacher
+ * reads the clean ob, and x, t_pdflat, s_pdflat's meaning, stepped_with, reward, actions and the
+ * training on every (clean) row with its own keep_prob dropout are as without faults.  They compose
+ * with the beta-coin and the action noise.  RDM_ACT_TEACHER calls evaluate no student: they ignore the
+ * setting and launch what they launch without it.  The mask is a function of (seed, env, episode,
+ * step, component) alone: it does not depend on the grid, the block size or the split of the steps
+ * over calls, and a captured call replays the NEXT steps' mask.  Mode, keep_prob and seed are kernel
+ * arguments: a captured call keeps the values it was captured with, whatever is set later.
+ * rdm_envs_set_obs_faults is host-only (no device call, no allocation, no synchronisation); the next
+ * call takes the new setting; it may precede rdm_envs_attach and survives attach and reset.
+ * rdm_evaluate never reads it.  RD_EINVAL, naming the function and the field, before the handle is
+ * read: NULL struct; unknown mode; keep_prob NaN, <= 0 or > 1; then a NULL trainer.
+ * rdm_envs_obs_faults copies the setting to *out (RD_EINVAL for a NULL trainer or out). */
+int rdm_envs_set_obs_faults(rdm_trainer* t, const rd_obs_faults* of);
+int rdm_envs_obs_faults(const rdm_trainer* t, rd_obs_faults* out);
+
+/* rdm_evaluate with the student reading its observation through *of (RD_OBS_DROPOUT or RD_OBS_MISSING)
+ * at Philox episode first_episode + e, with or without a draws table, and, with nz, its action
+ * perturbed as rdm_evaluate_noisy perturbs it (nz = NULL or mode RD_NOISE_NONE: the mean acts): the
+ * records (clean ob, T_s from the clean ob, S_s from the masked one), returns and final_dist of that
+ * trajectory.  Bitwise the stepwise loop { rdd_forward, rd_mask_obs, rdm_forward on the masked row,
+ * [rd_perturb_actions], rd_step }.  Independent of the envs' settings; capturable.
+ * RD_EINVAL as rdm_evaluate, and before it: NULL of, unknown mode, a bad keep_prob, mode =
+ * RD_OBS_CLEAN (call the plain function); a bad *nz as rdm_evaluate_noisy names it. */
+int rdm_evaluate_faulty(rdm_trainer* t, const rdm_eval_config* cfg, const rd_obs_faults* of, const rd_action_noise* nz,
+                        float* returns, float* final_dist, float* records);
 
 #ifdef __cplusplus
 }

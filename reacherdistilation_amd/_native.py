@@ -32,6 +32,11 @@ class RdActionNoise(ctypes.Structure):
     _fields_ = [("mode", I32), ("scale", F32), ("seed", U64)]
 
 
+class RdObsFaults(ctypes.Structure):
+    """rd_obs_faults (include/reacher_obs_faults.h); obs_faults.py builds and checks one"""
+    _fields_ = [("mode", I32), ("keep_prob", F32), ("seed", U64)]
+
+
 # (name, restype, argtypes) for every symbol include/*.h declares
 SIGNATURES = {
     # reacher.h
@@ -49,6 +54,8 @@ SIGNATURES = {
     "rd_last_error": (ctypes.c_char_p, []),
     # reacher_action_noise.h
     "rd_perturb_actions": (INT, [ctypes.POINTER(RdActionNoise), I64, I64, I32, I32, P, P, P, INT, P]),
+    # reacher_obs_faults.h
+    "rd_mask_obs": (INT, [ctypes.POINTER(RdObsFaults), I64, I64, I32, I32, P, P, P, INT, P]),
     # reacher_comm.h
     "rd_comm_unique_id": (INT, [P]),
     "rd_comm_probe": (INT, [INT]),

@@ -43,7 +43,8 @@ LDFLAGS = ["-shared", f"--offload-arch={ARCH}", "-ldl"]
 # product source is now scanned for it (tests/test_product_hygiene.py).
 NO_SLP = ["-fno-slp-vectorize"]
 SRC_FLAGS = {"distill.hip": NO_SLP, "ppo.hip": NO_SLP, "student_mlp.hip": NO_SLP, "student_mlp_mix.hip": NO_SLP,
-             "student_mlp_noise.hip": NO_SLP, "student_lstm.hip": NO_SLP, "student_lstm_noise.hip": NO_SLP}
+             "student_mlp_noise.hip": NO_SLP, "student_mlp_faults.hip": NO_SLP, "student_lstm.hip": NO_SLP,
+             "student_lstm_noise.hip": NO_SLP, "student_lstm_faults.hip": NO_SLP}
 
 
 def src_flags(path):

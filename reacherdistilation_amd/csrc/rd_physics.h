@@ -340,6 +340,35 @@ __device__ __forceinline__ void action_noise_apply(int32_t mode, float scale, fl
     }
 }
 
+// Sensor faults on the student's observation (include/reacher_obs_faults.h, the one definition): bit k
+// of the result = component k (0..10) of env `env_id`'s observation at step `step` of its episode is
+// kept, u01(word k % 4 of Philox(ctr = env_id lo, env_id hi, episode, 0x20000000 | (k / 4) << 8 | step;
+// key = seed)) < keep_prob.  Counter word 3 has bit 29 set and bits 30, 31 clear: disjoint from the
+// reset draws (0, 1), the action noise (bit 30) and the coins (bit 31) under one seed.
+__device__ __forceinline__ uint32_t obs_fault_keep(uint64_t seed, uint64_t env_id, int32_t episode, int32_t step,
+                                                   float keep_prob) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        uint32_t o[4];
+        philox((uint32_t)env_id, (uint32_t)(env_id >> 32), (uint32_t)episode,
+               0x20000000u | ((uint32_t)q << 8) | (uint32_t)step, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * q + j < kObsDim && u01(o[j]) < keep_prob) bits |= 1u << (4 * q + j);
+    }
+    return bits;
+}
+
+// What the student reads of component k under `mode` (RD_OBS_*: 0 clean, 1 dropout, 2 missing): a kept
+// reading as it is, or divided by keep_prob as the training kernels' dropout divides it; a lost one 0
+__device__ __forceinline__ float obs_fault_see(int32_t mode, float keep_prob, uint32_t bits, int k, float ob) {
+    FP_SOURCE_ROUNDING();
+    if (mode == 0) return ob;
+    const float kept = mode == 1 ? ob / keep_prob : ob;
+    return (bits >> k) & 1u ? kept : 0.0f;
+}
+
 // ------------------------------------------------------------------ envs a handle keeps on the device
 // (persistent envs: state [8][n], AUX rows of carried values [AUX][n], clock [2][n] = step of the
 // episode, episode.  student_lstm_envs.h calls these; student_mlp_envs.h has the same two bodies

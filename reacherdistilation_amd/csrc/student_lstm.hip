@@ -30,7 +30,9 @@
 // One translation unit: the device code is the ten student_lstm_*.h included below, in the order the
 // kernels stand in the object.  This file keeps rdl_trainer, the choice of launches for a batch
 // (Path), one function per cell path and head path, and the C ABI.  (The envs and evaluation kernels'
-// noisy instances, action noise, are compiled in student_lstm_noise.hip: student_lstm_noise.h.)
+// noisy instances, action noise, are compiled in student_lstm_noise.hip: student_lstm_noise.h; their
+// faulty instances, sensor faults on the student's observation, in student_lstm_faults.hip:
+// student_lstm_faults.h.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -45,7 +47,9 @@
 #include "rd_device.h"
 #include "rd_gemm.h"
 #include "rd_host.h"
+#include "rd_obs_faults.h"
 #include "rd_physics.h"
+#include "student_lstm_faults.h"
 #include "student_lstm_noise.h"
 
 namespace {
@@ -122,6 +126,9 @@ struct rdl_trainer {
     rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
     float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
     int64_t action_rows = 0;
+    // sensor faults on what the student reads in RDL_ACT_STUDENT calls (rdl_envs_set_obs_faults): a
+    // host-side setting of the handle too
+    rd_obs_faults faults{RD_OBS_CLEAN, 1.0f, 0};
 };
 
 namespace {
@@ -644,6 +651,14 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
     auto* kern = !stu ? student_lstm_envs_kernel<false, false>
                  : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
+    // sensor faults: the faulty instances for a student call (student_lstm_faults.hip); they carry the
+    // mixture and the noise too.  A teacher call evaluates no student and launches what it launched
+    if (stu && t->faults.mode != RD_OBS_CLEAN) {
+        const rd::LstmEnvsFaultLaunch l{&a, t->beta, t->coin_seed, t->noise, t->actions, t->faults, bf16_query(t), grid.x,
+                                        t->stream};
+        RD_HIP(rd::launch_lstm_envs_faulty(l), "student_lstm_envs_kernel (faulty) launch");
+        return RD_OK;
+    }
     // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
     // wants the actions (student_lstm_noise.hip); they carry the mixture too
     if (t->noise.mode != RD_NOISE_NONE || t->actions) {
@@ -962,8 +977,10 @@ int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, c
 
 namespace {
 
-// rdl_evaluate (nz = null) and rdl_evaluate_noisy, `fn` naming the caller
-int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
+// rdl_evaluate (nz = of = null), rdl_evaluate_noisy (of = null) and rdl_evaluate_faulty (nz = null: the
+// mean acts), `fn` naming the caller
+int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz,
+             const rd_obs_faults* of, const float* state0,
              float* returns, float* final_dist, float* records, float* state_out) {
     if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "%s: null trainer, config or returns", fn);
     if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
@@ -996,6 +1013,12 @@ int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const r
     a.T = t->T;
     // a block of 16 envs per workgroup for the whole launch, one workgroup per CU (its LDS)
     const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = cfg->grid > 0 ? cfg->grid : t->cus;
+    if (of) {   // the faulty instances (student_lstm_faults.hip)
+        const rd::LstmEvalFaultLaunch l{&a, nz ? *nz : rd_action_noise{RD_NOISE_NONE, 1.0f, 0}, *of, bf16_query(t),
+                                        (unsigned)(nblk < cap ? nblk : cap), t->stream};
+        RD_HIP(rd::launch_lstm_eval_faulty(l), "student_lstm_evaluate_kernel (faulty) launch");
+        return RD_OK;
+    }
     if (nz) {   // the noisy instances (student_lstm_noise.hip)
         const rd::LstmEvalNoiseLaunch l{&a, *nz, bf16_query(t), (unsigned)(nblk < cap ? nblk : cap), t->stream};
         RD_HIP(rd::launch_lstm_eval_noisy(l), "student_lstm_evaluate_kernel (noisy) launch");
@@ -1013,13 +1036,22 @@ extern "C" {
 
 int rdl_evaluate(rdl_trainer* t, const rdl_eval_config* cfg, const float* state0, float* returns, float* final_dist,
                  float* records, float* state_out) {
-    return evaluate("rdl_evaluate", t, cfg, nullptr, state0, returns, final_dist, records, state_out);
+    return evaluate("rdl_evaluate", t, cfg, nullptr, nullptr, state0, returns, final_dist, records, state_out);
 }
 
 int rdl_evaluate_noisy(rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz, const float* state0,
                        float* returns, float* final_dist, float* records, float* state_out) {
     if (int rc = rd::check_action_noise("rdl_evaluate_noisy", nz, false)) return rc;
-    return evaluate("rdl_evaluate_noisy", t, cfg, nz, state0, returns, final_dist, records, state_out);
+    return evaluate("rdl_evaluate_noisy", t, cfg, nz, nullptr, state0, returns, final_dist, records, state_out);
+}
+
+int rdl_evaluate_faulty(rdl_trainer* t, const rdl_eval_config* cfg, const rd_obs_faults* of, const rd_action_noise* nz,
+                        const float* state0, float* returns, float* final_dist, float* records, float* state_out) {
+    if (int rc = rd::check_obs_faults("rdl_evaluate_faulty", of, false)) return rc;
+    if (nz) {
+        if (int rc = rd::check_action_noise("rdl_evaluate_faulty", nz, true)) return rc;
+    }
+    return evaluate("rdl_evaluate_faulty", t, cfg, nz, of, state0, returns, final_dist, records, state_out);
 }
 
 int rdl_envs_reset(rdl_trainer* t) {
@@ -1103,6 +1135,19 @@ int rdl_envs_bind_actions(rdl_trainer* t, float* buf, int64_t rows) {
     if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdl_envs_bind_actions: rows %lld < 1", (long long)rows);
     t->actions = buf;
     t->action_rows = buf ? rows : 0;
+    return RD_OK;
+}
+
+int rdl_envs_set_obs_faults(rdl_trainer* t, const rd_obs_faults* of) {
+    if (int rc = rd::check_obs_faults("rdl_envs_set_obs_faults", of, true)) return rc;
+    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_obs_faults: null trainer");
+    t->faults = *of;
+    return RD_OK;
+}
+
+int rdl_envs_obs_faults(const rdl_trainer* t, rd_obs_faults* out) {
+    if (!t || !out) return rd::set_error(RD_EINVAL, "rdl_envs_obs_faults: null trainer or out");
+    *out = t->faults;
     return RD_OK;
 }
 

@@ -76,6 +76,18 @@ struct LsEnvsNoiseArgs : LsEnvsMixArgs {
 template <class ARGS> constexpr bool kNoisy = false;
 template <> constexpr bool kNoisy<LsEnvsNoiseArgs> = true;
 
+// the faulty instances' (rdl_envs_set_obs_faults: sensor faults on the student's observation,
+// include/reacher_obs_faults.h), compiled in student_lstm_faults.hip.  Derived from the noisy one, so
+// one faulty instance carries beta, the action noise and the faults as run-time arguments
+struct LsEnvsFaultArgs : LsEnvsNoiseArgs {
+    int32_t obs_mode;        // RD_OBS_* (include/reacher_obs_faults.h)
+    float obs_keep;          // keep_prob
+    uint64_t obs_seed;       // the mask's Philox key
+};
+template <> constexpr bool kNoisy<LsEnvsFaultArgs> = true;
+template <class ARGS> constexpr bool kFaulty = false;
+template <> constexpr bool kFaulty<LsEnvsFaultArgs> = true;
+
 // episode 0 of every env; clock and aux to 0 (rd_reset's arithmetic); q and hist are memset by the host
 __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -94,6 +106,14 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
 // (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
 // T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
 // Nothing else of the step changes: the record, (c, h), the ring and the windows are the plain call's.
+// kFaulty<ARGS> (sensor faults; a student instance, MIXED and kNoisy too, either of which may be off at
+// run time): columns 0..10 of the ring's x rows hold what the student READS of each record, masked by
+// the record's own (episode, step) -- the carried records at entry (the mask is a pure function, so
+// the handle's history stays clean and a call after a teacher call, a reset of the setting or a call
+// boundary masks them the same), record s in the env's lane beside the coin and the noise
+// (ls_fault_mask, before the step's first barrier).  The clean observations live beside the ring
+// (ls_fault_clean): the windows' ob_w and the history written back come from there, the teacher's SO
+// row and the records from the clean registers.
 template <bool STUDENT_ACTS, bool BF16Q, bool MIXED = false, class ARGS = LsEnvsArgs>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
     static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
@@ -113,6 +133,9 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             const int r = x / (T * EH_REC), y = x - r * (T * EH_REC), slot = y / EH_REC, c = y - slot * EH_REC;
             const int64_t er = row0 + r < n ? row0 + r : row0;
             const float v = a.hist[(er * T + slot) * EH_REC + c];
+            if constexpr (kFaulty<ARGS>) {
+                if (c < rd::kObsDim) ls_fault_clean()[slot][r][c] = v;
+            }
             if (c < rd::kObsDim) lds::Xr[slot][r][c] = v;
             else if (c < rd::kObsDim + 4) lds::Xr[slot][r][EH_PREV + c - rd::kObsDim] = v;
         }
@@ -132,6 +155,19 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             episode = a.clock[n + env];
         }
         __syncthreads();
+        if constexpr (kFaulty<ARGS>) {
+            // the carried records of the open episode, as the student read them: slot's record is the last
+            // j <= s - 1 with j % T = slot (none at s = 0, or where that j < 0: a stale slot no window reads)
+            static_assert(STUDENT_ACTS && EV_ROWS * EV_MAX_T <= EV_THREADS, "a thread per carried record");
+            if (tid < EV_ROWS * T && s > 0) {
+                const int r = tid / T, slot = tid - r * T;
+                const int j = s - 1 - (((s - 1 - slot) % T + T) % T);
+                const int64_t er = row0 + r < n ? row0 + r : row0;
+                if (j >= 0)
+                    ls_fault_mask(r, slot, a.obs_mode, a.obs_keep, a.obs_seed, (uint64_t)(a.env_base + er),
+                                  a.clock[n + er], j, nullptr);
+            }
+        }
         if (STUDENT_ACTS) {   // the carried records' x rows, from their raw prev and THIS call's Wp, bp
             for (int slot = 0; slot < T; ++slot)
                 lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, true, &lds::Xr[slot][q.dr][EH_PREV]);
@@ -145,12 +181,17 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             if (phys) {   // record s, and its raw prev = T_{s-1} (zero at s = 0) into the ring
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
-                if constexpr (kNoisy<ARGS>)
-                    ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), episode, s);
+                if constexpr (kNoisy<ARGS>) {
+                    if (!kFaulty<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                        ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), episode, s);
+                }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) lds::Xr[slot][lane][EH_PREV + c] = s ? lds::TO[(s - 1) & 1][lane][c] : 0.0f;
                 if constexpr (MIXED) ls_record_head(lane, slot, st, rec, carry, coin ? 0.0f : 1.0f);
                 else ls_record_head(lane, slot, st, rec, carry, STUDENT_ACTS ? 1.0f : 0.0f);
+                if constexpr (kFaulty<ARGS>)
+                    ls_fault_mask(lane, slot, a.obs_mode, a.obs_keep, a.obs_seed, (uint64_t)(a.env_base + env), episode, s,
+                                  ls_fault_clean());
             }
             // prev . Wp + bp of record s
             if (STUDENT_ACTS) lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
@@ -165,8 +206,13 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
                     const int p = x / (EV_ROWS * rd::kObsDim), y = x - p * (EV_ROWS * rd::kObsDim);
                     const int r = y / rd::kObsDim, c = y - r * rd::kObsDim;
                     const int64_t w = wrow + r;
-                    if (row0 + r < n && w < a.windows)
-                        a.ob_w[((int64_t)p * a.windows + w) * rd::kObsDim + c] = lds::Xr[(s - (T - 1) + p) % T][r][c];
+                    if constexpr (kFaulty<ARGS>) {   // the clean observations
+                        if (row0 + r < n && w < a.windows)
+                            a.ob_w[((int64_t)p * a.windows + w) * rd::kObsDim + c] = ls_fault_clean()[(s - (T - 1) + p) % T][r][c];
+                    } else {
+                        if (row0 + r < n && w < a.windows)
+                            a.ob_w[((int64_t)p * a.windows + w) * rd::kObsDim + c] = lds::Xr[(s - (T - 1) + p) % T][r][c];
+                    }
                 }
                 for (int x = tid; x < T * EV_ROWS * 4; x += EV_THREADS) {
                     const int p = x / (EV_ROWS * 4), r = (x >> 2) & (EV_ROWS - 1), c = x & 3;
@@ -209,9 +255,15 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
         if (STUDENT_ACTS) ls_state_store(tid, a.q, n, row0, hp);
         for (int x = tid; x < EV_ROWS * T * EH_REC; x += EV_THREADS) {
             const int r = x / (T * EH_REC), y = x - r * (T * EH_REC), slot = y / EH_REC, c = y - slot * EH_REC;
-            if (row0 + r < n)
-                a.hist[((row0 + r) * T + slot) * EH_REC + c] =
-                    c < rd::kObsDim ? lds::Xr[slot][r][c] : c < rd::kObsDim + 4 ? lds::Xr[slot][r][EH_PREV + c - rd::kObsDim] : 0.0f;
+            if constexpr (kFaulty<ARGS>) {   // the clean observations
+                if (row0 + r < n)
+                    a.hist[((row0 + r) * T + slot) * EH_REC + c] =
+                        c < rd::kObsDim ? ls_fault_clean()[slot][r][c] : c < rd::kObsDim + 4 ? lds::Xr[slot][r][EH_PREV + c - rd::kObsDim] : 0.0f;
+            } else {
+                if (row0 + r < n)
+                    a.hist[((row0 + r) * T + slot) * EH_REC + c] =
+                        c < rd::kObsDim ? lds::Xr[slot][r][c] : c < rd::kObsDim + 4 ? lds::Xr[slot][r][EH_PREV + c - rd::kObsDim] : 0.0f;
+            }
         }
         if (valid) {
             rd::store_state(a.state, n, env, st);

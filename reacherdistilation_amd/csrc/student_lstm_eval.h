@@ -42,6 +42,20 @@ struct LsEvalNoiseArgs : LsEvalArgs {
 template <class ARGS> constexpr bool kNoisyEval = false;
 template <> constexpr bool kNoisyEval<LsEvalNoiseArgs> = true;
 
+// rdl_evaluate_faulty's instances (student_lstm_faults.hip): the student reads its observations through
+// the sensor faults (include/reacher_obs_faults.h) at Philox episode first_episode + e; its action may
+// be perturbed too (noise_mode = RD_NOISE_NONE: the mean acts).  The env's lane masks record s in the
+// ring (ls_fault_mask) beside the noise, before the step's first barrier; the record keeps that mask in
+// the later windows that hold it.  The teacher's row and the records keep the clean observation
+struct LsEvalFaultArgs : LsEvalNoiseArgs {
+    int32_t obs_mode;        // RD_OBS_DROPOUT or RD_OBS_MISSING
+    float obs_keep;          // keep_prob
+    uint64_t obs_seed;
+};
+template <> constexpr bool kNoisyEval<LsEvalFaultArgs> = true;
+template <class ARGS> constexpr bool kFaultyEval = false;
+template <> constexpr bool kFaultyEval<LsEvalFaultArgs> = true;
+
 template <bool BF16Q, class ARGS = LsEvalArgs>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS a) {
     const LsThread q = ls_prologue(a.tnet, a.P, a.img, a.T);
@@ -75,9 +89,15 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS 
                 const int slot = s % T;
                 float* rec = rec0 ? rec0 + s * EV_REC : nullptr;
                 if constexpr (kNoisyEval<ARGS>) {
-                    if (phys) ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s);
+                    if (phys && (!kFaultyEval<ARGS> || a.noise_mode != 0))   // a faulty call's noise may be off
+                        ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s);
                 }
                 if (phys) ls_record_head(lane, slot, st, rec, carry, 1.0f);
+                if constexpr (kFaultyEval<ARGS>) {
+                    if (phys)
+                        ls_fault_mask(lane, slot, a.obs_mode, a.obs_keep, a.obs_seed, (uint64_t)(a.env_base + env),
+                                      a.first_episode + e, s, nullptr);
+                }
                 // prev . Wp + bp of record s: prev = T_{s-1}, zero at s = 0
                 lds::Xr[slot][q.dr][11 + q.dc] = ls_dense(q, s != 0, lds::TO[(s - 1) & 1][q.dr]);
                 __syncthreads();

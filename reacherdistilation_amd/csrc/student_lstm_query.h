@@ -323,3 +323,28 @@ __device__ __forceinline__ void ls_noise_draw(int lane, uint64_t seed, uint64_t 
     ls_noise_park()[2 * lane] = xi0;
     ls_noise_park()[2 * lane + 1] = xi1;
 }
+
+// The faulty instances' pieces (sensor faults on the student's observation,
+// include/reacher_obs_faults.h; student_lstm_faults.hip).  The positions read a record's observation
+// from columns 0..10 of its x row in the ring, so that is where the mask goes: ls_fault_mask replaces
+// row `row` of slot `slot`, record (episode, step) of env `env_id`, by what the student reads of it
+// (rd::obs_fault_keep, rd::obs_fault_see) and, with `clean`, copies the clean readings there first.
+// The record keeps that mask in every later query that still holds it; the zero record's row (Xz) is
+// never touched.  The teacher's SO row and the record written to global memory keep the clean values.
+// ls_fault_clean: the envs kernel's clean copy of the ring's observations, which its windows and the
+// handle's history are written from; only the instances that call it carry the 11 KiB.
+__device__ __forceinline__ float (*ls_fault_clean())[EV_ROWS][rd::kObsDim] {
+    __shared__ float ob[EV_MAX_T][EV_ROWS][rd::kObsDim];
+    return ob;
+}
+__device__ __forceinline__ void ls_fault_mask(int row, int slot, int32_t mode, float keep_prob, uint64_t seed,
+                                              uint64_t env_id, int32_t episode, int32_t step,
+                                              float (*clean)[EV_ROWS][rd::kObsDim]) {
+    const uint32_t keep = rd::obs_fault_keep(seed, env_id, episode, step, keep_prob);
+#pragma unroll
+    for (int k = 0; k < rd::kObsDim; ++k) {
+        const float v = lds::Xr[slot][row][k];
+        if (clean) clean[slot][row][k] = v;
+        lds::Xr[slot][row][k] = rd::obs_fault_see(mode, keep_prob, keep, k, v);
+    }
+}

@@ -28,7 +28,9 @@
 // student_mlp_envs.h, their common step in student_mlp_query.h.  This file keeps rdm_trainer, the
 // choice of the row block, one launch function per kernel family, and the C ABI.  (The envs kernel's
 // mixed instances, DAgger's beta-mixture, are compiled in student_mlp_mix.hip: student_mlp_mix.h; the
-// envs and evaluation kernels' noisy instances in student_mlp_noise.hip: student_mlp_noise.h.)
+// envs and evaluation kernels' noisy instances in student_mlp_noise.hip: student_mlp_noise.h; their
+// faulty instances, sensor faults on the student's observation, in student_mlp_faults.hip:
+// student_mlp_faults.h.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -40,7 +42,9 @@
 #include "rd_common.h"
 #include "rd_device.h"
 #include "rd_host.h"
+#include "rd_obs_faults.h"
 #include "rd_physics.h"
+#include "student_mlp_faults.h"
 #include "student_mlp_mix.h"
 #include "student_mlp_noise.h"
 
@@ -99,6 +103,9 @@ struct rdm_trainer {
     rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
     float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
     int64_t action_rows = 0;
+    // sensor faults on what the student reads in RDM_ACT_STUDENT calls (rdm_envs_set_obs_faults): a
+    // host-side setting of the handle too
+    rd_obs_faults faults{RD_OBS_CLEAN, 1.0f, 0};
 };
 
 namespace {
@@ -257,6 +264,14 @@ int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdfl
     auto* kern = stu && t->bf ? (b.small ? student_mlp_envs_kernel<16, true, true> : student_mlp_envs_kernel<64, true, true>)
                  : b.small    ? (stu ? student_mlp_envs_kernel<16, true, false> : student_mlp_envs_kernel<16, false, false>)
                               : (stu ? student_mlp_envs_kernel<64, true, false> : student_mlp_envs_kernel<64, false, false>);
+    // sensor faults: the faulty instances for a student call (student_mlp_faults.hip); they carry the
+    // mixture and the noise too.  A teacher call evaluates no student and launches what it launched
+    if (stu && t->faults.mode != RD_OBS_CLEAN) {
+        const rd::MlpEnvsFaultLaunch l{&a, t->beta, t->coin_seed, t->flags, t->noise, t->actions, t->faults, t->bf,
+                                       b.small, b.grid, b.threads, t->stream};
+        RD_HIP(rd::launch_mlp_envs_faulty(l), "student_mlp_envs_kernel (faulty) launch");
+        return RD_OK;
+    }
     // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
     // wants the actions (student_mlp_noise.hip); they carry the mixture too
     if (t->noise.mode != RD_NOISE_NONE || t->actions) {
@@ -471,9 +486,10 @@ int rdm_set_teacher(rdm_trainer* t, const float* params, const float* ob_mean, c
 
 namespace {
 
-// rdm_evaluate (nz = null) and rdm_evaluate_noisy, `fn` naming the caller
-int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz, float* returns,
-             float* final_dist, float* records) {
+// rdm_evaluate (nz = of = null), rdm_evaluate_noisy (of = null) and rdm_evaluate_faulty (nz = null: the
+// mean acts), `fn` naming the caller
+int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz,
+             const rd_obs_faults* of, float* returns, float* final_dist, float* records) {
     if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "%s: null trainer, config or returns", fn);
     if (cfg->n_envs < 1 || cfg->n_envs > ((int64_t)1 << 31))
         return rd::set_error(RD_EINVAL, "%s: n_envs %lld outside 1 .. 2^31", fn, (long long)cfg->n_envs);
@@ -497,6 +513,12 @@ int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const r
     a.first_episode = cfg->first_episode;
     // a block of envs per workgroup for the whole launch, sized as rdm_forward sizes its row block
     const Blocks b = blocks_of(a.n, cfg->grid > 0 ? cfg->grid : t->grid, eval_small_rows, true);
+    if (of) {   // the faulty instances (student_mlp_faults.hip)
+        const rd::MlpEvalFaultLaunch l{&a, nz ? *nz : rd_action_noise{RD_NOISE_NONE, 1.0f, 0}, *of, t->bf, b.small,
+                                       b.grid, b.threads, t->stream};
+        RD_HIP(rd::launch_mlp_eval_faulty(l), "student_mlp_evaluate_kernel (faulty) launch");
+        return RD_OK;
+    }
     if (nz) {   // the noisy instances (student_mlp_noise.hip)
         const rd::MlpEvalNoiseLaunch l{&a, *nz, t->bf, b.small, b.grid, b.threads, t->stream};
         RD_HIP(rd::launch_mlp_eval_noisy(l), "student_mlp_evaluate_kernel (noisy) launch");
@@ -514,13 +536,22 @@ int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const r
 extern "C" {
 
 int rdm_evaluate(rdm_trainer* t, const rdm_eval_config* cfg, float* returns, float* final_dist, float* records) {
-    return evaluate("rdm_evaluate", t, cfg, nullptr, returns, final_dist, records);
+    return evaluate("rdm_evaluate", t, cfg, nullptr, nullptr, returns, final_dist, records);
 }
 
 int rdm_evaluate_noisy(rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz, float* returns,
                        float* final_dist, float* records) {
     if (int rc = rd::check_action_noise("rdm_evaluate_noisy", nz, false)) return rc;
-    return evaluate("rdm_evaluate_noisy", t, cfg, nz, returns, final_dist, records);
+    return evaluate("rdm_evaluate_noisy", t, cfg, nz, nullptr, returns, final_dist, records);
+}
+
+int rdm_evaluate_faulty(rdm_trainer* t, const rdm_eval_config* cfg, const rd_obs_faults* of, const rd_action_noise* nz,
+                        float* returns, float* final_dist, float* records) {
+    if (int rc = rd::check_obs_faults("rdm_evaluate_faulty", of, false)) return rc;
+    if (nz) {
+        if (int rc = rd::check_action_noise("rdm_evaluate_faulty", nz, true)) return rc;
+    }
+    return evaluate("rdm_evaluate_faulty", t, cfg, nz, of, returns, final_dist, records);
 }
 
 int rdm_envs_reset(rdm_trainer* t) {
@@ -603,6 +634,19 @@ int rdm_envs_bind_actions(rdm_trainer* t, float* buf, int64_t rows) {
     if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_actions: rows %lld < 1", (long long)rows);
     t->actions = buf;
     t->action_rows = buf ? rows : 0;
+    return RD_OK;
+}
+
+int rdm_envs_set_obs_faults(rdm_trainer* t, const rd_obs_faults* of) {
+    if (int rc = rd::check_obs_faults("rdm_envs_set_obs_faults", of, true)) return rc;
+    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_obs_faults: null trainer");
+    t->faults = *of;
+    return RD_OK;
+}
+
+int rdm_envs_obs_faults(const rdm_trainer* t, rd_obs_faults* out) {
+    if (!t || !out) return rd::set_error(RD_EINVAL, "rdm_envs_obs_faults: null trainer or out");
+    *out = t->faults;
     return RD_OK;
 }
 

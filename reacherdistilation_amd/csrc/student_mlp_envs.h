@@ -58,6 +58,18 @@ struct SmEnvsNoiseArgs : SmEnvsMixArgs {
 template <class ARGS> constexpr bool kNoisy = false;
 template <> constexpr bool kNoisy<SmEnvsNoiseArgs> = true;
 
+// the faulty instances' (rdm_envs_set_obs_faults: sensor faults on the student's observation,
+// include/reacher_obs_faults.h), compiled in student_mlp_faults.hip.  Derived from the noisy one, so
+// one faulty instance carries beta, the action noise and the faults as run-time arguments
+struct SmEnvsFaultArgs : SmEnvsNoiseArgs {
+    int32_t obs_mode;        // RD_OBS_* (include/reacher_obs_faults.h)
+    float obs_keep;          // keep_prob
+    uint64_t obs_seed;       // the mask's Philox key
+};
+template <> constexpr bool kNoisy<SmEnvsFaultArgs> = true;
+template <class ARGS> constexpr bool kFaulty = false;
+template <> constexpr bool kFaulty<SmEnvsFaultArgs> = true;
+
 // episode 0 of every env; clocks, carried reward and previous fields to 0 (rd_reset's arithmetic)
 __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -78,6 +90,11 @@ __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs 
 // (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
 // T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
 // Nothing else of the step changes.
+// kFaulty<ARGS> (sensor faults; a student instance, MIXED and kNoisy too, either of which may be off at
+// run time): the env's lane draws this record's keep bits beside the coin and the noise
+// (rd::obs_fault_keep, three Philox calls before the step's first barrier) and overwrites the
+// observation part of its X0 row with rd::obs_fault_see of them.  Only the student's layer 0 reads X0:
+// the teacher's SO row, x and every other output keep the clean registers.
 template <int ROWS, bool STUDENT_ACTS, bool BF, bool MIXED = false, class ARGS = SmEnvsArgs>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(ARGS a) {
     // MIXED: the teacher steps this lane's env now.  The kernel's first local: declared inside the step
@@ -114,10 +131,20 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(A
             if (phys) {
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
-                if constexpr (kNoisy<ARGS>)
-                    rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), episode, s, xi0, xi1);
+                if constexpr (kNoisy<ARGS>) {
+                    if (!kFaulty<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                        rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), episode, s, xi0, xi1);
+                }
                 float row[RDM_IN];
                 qs_row<ROWS, STUDENT_ACTS>(lds, lane, st, s, tp, prev_field, row);
+                if constexpr (kFaulty<ARGS>) {
+                    static_assert(STUDENT_ACTS, "the faults are on what the student reads");
+                    const uint32_t keep = rd::obs_fault_keep(a.obs_seed, (uint64_t)(a.env_base + env), episode, s, a.obs_keep);
+                    float* X0 = lds + Lay<ROWS>::O_X0;
+#pragma unroll
+                    for (int c = 0; c < rd::kObsDim; ++c)
+                        X0[lane * S_X0 + pk(c)] = rd::obs_fault_see(a.obs_mode, a.obs_keep, keep, c, row[c]);
+                }
                 if (valid) {
                     f32x4* xo = reinterpret_cast<f32x4*>(a.x + out * RDM_IN);
 #pragma unroll

@@ -34,6 +34,20 @@ struct SmEvalNoiseArgs : SmEvalArgs {
 template <class ARGS> constexpr bool kNoisyEval = false;
 template <> constexpr bool kNoisyEval<SmEvalNoiseArgs> = true;
 
+// rdm_evaluate_faulty's instances (student_mlp_faults.hip): the student reads its observation through
+// the sensor faults (include/reacher_obs_faults.h) at Philox episode first_episode + e; its action may
+// be perturbed too (noise_mode = RD_NOISE_NONE: the mean acts).  The env's lane draws the keep bits
+// beside the noise and overwrites the observation part of its X0 row; the teacher's row and the
+// records keep the clean registers
+struct SmEvalFaultArgs : SmEvalNoiseArgs {
+    int32_t obs_mode;        // RD_OBS_DROPOUT or RD_OBS_MISSING
+    float obs_keep;          // keep_prob
+    uint64_t obs_seed;
+};
+template <> constexpr bool kNoisyEval<SmEvalFaultArgs> = true;
+template <class ARGS> constexpr bool kFaultyEval = false;
+template <> constexpr bool kFaultyEval<SmEvalFaultArgs> = true;
+
 template <int ROWS, bool BF, class ARGS = SmEvalArgs>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kernel(ARGS a) {
     // kNoisyEval: the step's draws.  The kernel's first locals, as student_mlp_envs_kernel's coin is:
@@ -66,10 +80,20 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
             float* rec = a.records && valid ? a.records + ((int64_t)e * n + env) * (rd::kEpisodeSteps * EREC) : nullptr;
             for (int s = 0; s < rd::kEpisodeSteps; ++s) {
                 if (phys) {
-                    if constexpr (kNoisyEval<ARGS>)
-                        rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s, xi0, xi1);
+                    if constexpr (kNoisyEval<ARGS>) {
+                        if (!kFaultyEval<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                            rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s, xi0, xi1);
+                    }
                     float row[RDM_IN];
                     qs_row<ROWS, true>(lds, lane, st, s, tp, prev_field, row);
+                    if constexpr (kFaultyEval<ARGS>) {
+                        const uint32_t keep = rd::obs_fault_keep(a.obs_seed, (uint64_t)(a.env_base + env),
+                                                                 a.first_episode + e, s, a.obs_keep);
+                        float* X0 = lds + Lay<ROWS>::O_X0;
+#pragma unroll
+                        for (int c = 0; c < rd::kObsDim; ++c)
+                            X0[lane * S_X0 + pk(c)] = rd::obs_fault_see(a.obs_mode, a.obs_keep, keep, c, row[c]);
+                    }
                     if (rec) {
                         float* r = rec + s * EREC;
 #pragma unroll

@@ -72,7 +72,8 @@ def evaluate_policy(params: MlpPolicyParams, episodes: int, *, n_envs: int | Non
 
 def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, episodes: int, *,
                          n_envs: int | None = None, seed: int = 0, reset: str = "gym", device="cuda:0",
-                         noise: str = "none", noise_scale: float = 1.0, noise_seed: int | None = None) -> np.ndarray:
+                         noise: str = "none", noise_scale: float = 1.0, noise_seed: int | None = None,
+                         faults=None) -> np.ndarray:
     """evaluate_policy for the reference student: the 50-step returns of its mean action over
     ``episodes`` student-stepped episodes, in one launch (StudentMlpTrainer.evaluate).
     ``trainer_or_params`` is a StudentMlpTrainer (evaluated as it stands, on its device; ``teacher``
@@ -83,7 +84,9 @@ def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, epi
     Returns a float32 array [episodes] in (round, env) order; ``n_envs`` (default: one env per
     episode), ``seed`` and ``reset`` as evaluate_policy.  ``noise``, ``noise_scale``, ``noise_seed``:
     StudentMlpTrainer.evaluate's -- the returns under perturbed actions ("policy": the policy sampled;
-    "fixed": an isotropic sigma), noise_seed defaulting to ``seed``."""
+    "fixed": an isotropic sigma), noise_seed defaulting to ``seed``.  ``faults``: StudentMlpTrainer.evaluate's
+    -- the returns with the student reading its observation through sensor faults, e.g.
+    ("missing", 0.9)."""
     if reset not in ("gym", "philox"):
         raise ValueError(f"unknown reset mode {reset!r}")
     episodes = int(episodes)
@@ -99,7 +102,7 @@ def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, epi
             tr.set_teacher(teacher)
         draws = gym_draw_table(seed, n, E) if reset == "gym" else None
         ret = tr.evaluate(n, E, seed=seed, draws=draws, noise=noise, noise_scale=noise_scale,
-                          noise_seed=noise_seed).returns
+                          noise_seed=noise_seed, faults=faults).returns
         return ret.reshape(-1)[:episodes].cpu().numpy()
     finally:
         if own:
@@ -109,7 +112,8 @@ def evaluate_student_mlp(trainer_or_params, teacher: MlpPolicyParams | None, epi
 def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, episodes: int, *,
                           n_envs: int | None = None, seed: int = 0, reset: str = "gym", device="cuda:0",
                           steps: int = STEPS_UNROLLED, dtype: str = "f32", query_dtype: str = "f32",
-                          noise: str = "none", noise_scale: float = 1.0, noise_seed: int | None = None) -> np.ndarray:
+                          noise: str = "none", noise_scale: float = 1.0, noise_seed: int | None = None,
+                          faults=None) -> np.ndarray:
     """evaluate_student_mlp for the reference's LSTM student: the 50-step returns of its mean action
     over ``episodes`` student-stepped episodes, in one rollout launch (StudentLstmTrainer.evaluate).
     ``trainer_or_params`` is a StudentLstmTrainer (evaluated as it stands, on its device; ``teacher``
@@ -121,7 +125,7 @@ def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, ep
     ``reset`` as evaluate_policy.  ``dtype`` and ``query_dtype`` are StudentLstmConfig's for the trainer
     made from a parameter vector (dtype="bf16", query_dtype="bf16": the policy as deployed on the bf16
     cell); a given trainer is evaluated with its own setting.  ``noise``, ``noise_scale``, ``noise_seed``:
-    StudentLstmTrainer.evaluate's, as in evaluate_student_mlp."""
+    StudentLstmTrainer.evaluate's, as in evaluate_student_mlp; so is ``faults``."""
     if reset not in ("gym", "philox"):
         raise ValueError(f"unknown reset mode {reset!r}")
     episodes = int(episodes)
@@ -138,7 +142,7 @@ def evaluate_student_lstm(trainer_or_params, teacher: MlpPolicyParams | None, ep
             tr.set_teacher(teacher)
         draws = gym_draw_table(seed, n, E) if reset == "gym" else None
         ret = tr.evaluate(n, E, seed=seed, draws=draws, noise=noise, noise_scale=noise_scale,
-                          noise_seed=noise_seed).returns
+                          noise_seed=noise_seed, faults=faults).returns
         return ret.reshape(-1)[:episodes].cpu().numpy()
     finally:
         if own:

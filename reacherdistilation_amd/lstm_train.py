@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import torch
 
+from . import obs_faults as obf
 from .config import LSTM_BATCH_SIZE, MAX_CAPACITY, STEPS_UNROLLED, TOTAL_EPISODES
 from .dataset import DeviceDataset
 from .distill import DistillConfig, DistillTrainer
@@ -119,7 +120,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, query_dtype: str = "f32",
                beta0: float = 0.0, beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0,
-               replay_priority: str = "none"):
+               replay_priority: str = "none", faults=None, eval_faults=None):
     """Batched on-policy distillation of the LSTM student (student_lstm_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each one
     StudentLstmTrainer.step_envs call: ``accum_steps`` (a multiple of 50) env steps of every env in one
@@ -161,6 +162,10 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     (StudentLstmTrainer.set_action_noise, keyed by ``seed``): "fixed" with the teacher acting
     (warmup_steps = opt_steps) is DART's noisy expert, "policy" samples whoever acts.  The evaluations
     stay noiseless.  The default "none" is the same launches as before.
+    ``faults``: sensor faults on what the acting student reads in every envs call of the run
+    (StudentLstmTrainer.set_obs_faults, keyed by ``seed``), as evaluate's ``faults``: ("dropout" | "missing",
+    keep_prob).  The windows it trains on stay clean.  ``eval_faults``: the same for the periodic
+    evaluation (StudentLstmTrainer.evaluate(faults=)).  The defaults (None) are the same launches as before.
     ``replay_priority`` (needs a ring): "record" draws the batches in proportion to the records' priorities
     (ReplayRing.enable_priorities: the student's squared action error against the teacher) instead of
     uniformly; a push writes the priorities from the record's own s_pdflat, the student as it acted, or
@@ -190,6 +195,9 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     st.attach_envs(n, seed=seed, accum_steps=K)
     if noise != "none":
         st.set_action_noise(noise, noise_scale)
+    of = obf.parse(faults, seed)
+    if of is not None:
+        st.set_obs_faults(obf.MODE_NAMES[of.mode], of.keep_prob, of.seed)
     rew = torch.zeros(steps, device=st.device)
     evals = []
     ring = None
@@ -222,7 +230,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
             st.step(ob_w, prev_w, t_w)
             rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:
-            evals.append((k + 1, float(st.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
+            evals.append((k + 1, float(st.evaluate(int(eval_envs), 1, seed=seed + 1, faults=eval_faults).returns.mean())))
     m = st.metrics(steps)
     rew = rew.cpu().tolist()
     history = [(k + 1, float(m[k, 0]), float(m[k, 1] / (2 * m[k, 2])), rew[k]) for k in range(steps)]

@@ -30,6 +30,7 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
+from . import obs_faults as obf
 from .config import EPISODE_STEPS, LSTM_BATCH_SIZE, MLP_BATCH_SIZE, MLP_EPISODE_BUDGET, OBSPACE_SHAPE, STEPS_UNROLLED
 from .dataset import DeviceDataset
 from .pages import PageStore
@@ -122,7 +123,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                eval_every: int = 0, eval_envs: int = 4096, dtype: str = "f32", replay_capacity: int = 0,
                replay_windows: int = 0, updates_per_act: int = 1, replay_recent: int = 0, beta0: float = 0.0,
                beta_decay: float = 1.0, noise: str = "none", noise_scale: float = 1.0,
-               replay_priority: str = "none"):
+               replay_priority: str = "none", faults=None, eval_faults=None):
     """Batched on-policy distillation of the reference student (student_mlp_graph with input dropout
     ``keep_prob``): ``n_envs`` persistent lockstep envs, ``opt_steps`` optimiser steps, each on the
     ``accum_steps`` x n_envs rows of one StudentMlpTrainer.step_envs call (one env launch, the
@@ -161,7 +162,11 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     the maximum priority when the teacher stepped the act call (s_pdflat is zero there and says nothing
     about the student).  "refresh" also re-scores every sampled batch with the current student (one
     forward per optimiser step, ReplayRing.update_priorities) before it trains on it.  The default
-    "none" is the uniform loop, the same launches as before."""
+    "none" is the uniform loop, the same launches as before.
+    ``faults``: sensor faults on what the acting student reads in every envs call of the run
+    (StudentMlpTrainer.set_obs_faults, keyed by ``seed``), as evaluate's ``faults``: ("dropout" | "missing",
+    keep_prob).  The rows it trains on stay clean.  ``eval_faults``: the same for the periodic evaluation
+    (StudentMlpTrainer.evaluate(faults=)).  The defaults (None) are the same launches as before."""
     from .policy import synthetic_teacher
     n, steps, K = int(n_envs), int(opt_steps), int(accum_steps)
     if steps < 1 or not 0 <= int(warmup_steps) <= steps:
@@ -181,6 +186,9 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
     sm.attach_envs(n, seed=seed, accum_steps=K)
     if noise != "none":
         sm.set_action_noise(noise, noise_scale)
+    of = obf.parse(faults, seed)
+    if of is not None:
+        sm.set_obs_faults(obf.MODE_NAMES[of.mode], of.keep_prob, of.seed)
     rew = torch.zeros(steps, device=sm.device)
     evals = []
     ring = None
@@ -213,7 +221,7 @@ def train_envs(n_envs: int, opt_steps: int, *, keep_prob: float = 1.0, loss: str
                 sm.step(x, t)
             rew[k] = mean_reward
         if eval_every and (k + 1) % int(eval_every) == 0:
-            evals.append((k + 1, float(sm.evaluate(int(eval_envs), 1, seed=seed + 1).returns.mean())))
+            evals.append((k + 1, float(sm.evaluate(int(eval_envs), 1, seed=seed + 1, faults=eval_faults).returns.mean())))
     m = sm.metrics(steps)
     rew = rew.cpu().tolist()
     history = [(k + 1, float(m[k, 0]), float(m[k, 1] / (2 * m[k, 2])), rew[k]) for k in range(steps)]

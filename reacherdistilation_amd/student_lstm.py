@@ -30,6 +30,7 @@ import torch
 
 from . import _native as nat
 from . import action_noise as an
+from . import obs_faults as obf
 from .config import LSTM_BATCH_SIZE, NUM_UNITS, OBSPACE_SHAPE, PDFLAT_SHAPE, STEPS_UNROLLED
 from .dist import allreduce_sum_
 from .distill import EvalResult
@@ -91,6 +92,10 @@ nat.register({
     "rdl_envs_set_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
     "rdl_envs_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
     "rdl_envs_bind_actions": (INT, [P, P, I64]),
+    "rdl_envs_set_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
+    "rdl_envs_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
+    "rdl_evaluate_faulty": (INT, [P, ctypes.POINTER(RdlEvalConfig), ctypes.POINTER(nat.RdObsFaults),
+                                  ctypes.POINTER(nat.RdActionNoise), P, P, P, P, P]),
     "rdl_evaluate_noisy": (INT, [P, ctypes.POINTER(RdlEvalConfig), ctypes.POINTER(nat.RdActionNoise), P, P, P, P, P]),
     "rdl_set_teacher": (INT, [P, P, P, P]),
     "rdl_evaluate": (INT, [P, ctypes.POINTER(RdlEvalConfig), P, P, P, P, P]),
@@ -222,6 +227,7 @@ class StudentLstmTrainer:
         self._envs = None     # attach_envs()'s buffers
         self._envs_seed, self._coin_seed = 0, None   # set_teacher_share
         self._noise, self._noise_seed, self._actions = ("none", 1.0), None, None   # set_action_noise, actions
+        self._faults, self._faults_seed = ("none", 1.0), None   # set_obs_faults
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -379,7 +385,7 @@ class StudentLstmTrainer:
     def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
                  first_episode: int = 0, draws=None, state0=None, final_dist: bool = False, records: bool = False,
                  final_state: bool = False, grid: int = 0, noise: str = "none", noise_scale: float = 1.0,
-                 noise_seed: int | None = None) -> EvalResult:
+                 noise_seed: int | None = None, faults=None) -> EvalResult:
         """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
         with this student's mean action in ONE rollout launch (rdl_evaluate): the query loop of
         lstm_train.train without the optimiser steps, each env being column B-1 of the driver's
@@ -400,8 +406,15 @@ class StudentLstmTrainer:
         perturbed, a = mean + noise_scale (exp(logstd) | 1) xi with xi keyed (noise_seed, env_base + i,
         first_episode + e, step) -- the return under perturbed actions, bitwise the stepwise loop with
         action_noise.perturb_actions before the step.  ``noise_seed`` defaults to ``seed``.  The envs'
-        set_action_noise is never read here: the default is the noiseless return."""
+        set_action_noise is never read here: the default is the noiseless return.
+        ``faults`` = ("dropout" | "missing", keep_prob[, seed]) or a dict of them (rdl_evaluate_faulty;
+        obs_faults.py): the student reads every record of its windows through that mask, record j of an
+        episode keyed (seed, env_base + i, first_episode + e, j, component) wherever in a window it
+        stands, the seed defaulting to ``seed``; the teacher and the records keep the clean observation.
+        Composes with ``noise``.  Bitwise the stepwise loop with obs_faults.mask_obs on every record as it
+        enters the window.  The envs' set_obs_faults is never read here."""
         nz = an.native(noise, noise_scale, seed if noise_seed is None else noise_seed)
+        of = obf.parse(faults, seed)
         n, E = int(n_envs), int(episodes)
         if n < 1 or E < 1:
             raise ValueError("n_envs >= 1 and episodes >= 1")
@@ -428,7 +441,11 @@ class StudentLstmTrainer:
         out = (nat.ptr(state0) if state0 is not None else None, nat.ptr(res.returns),
                nat.ptr(res.final_dist) if final_dist else None, nat.ptr(res.records) if records else None,
                nat.ptr(res.state) if final_state else None)
-        if noise == "none":
+        if of is not None:
+            nat.check(self._lib.rdl_evaluate_faulty(self._h, ctypes.byref(c), ctypes.byref(of),
+                                                    None if noise == "none" else ctypes.byref(nz), *out),
+                      "rdl_evaluate_faulty")
+        elif noise == "none":
             nat.check(self._lib.rdl_evaluate(self._h, ctypes.byref(c), *out), "rdl_evaluate")
         else:
             nat.check(self._lib.rdl_evaluate_noisy(self._h, ctypes.byref(c), ctypes.byref(nz), *out),
@@ -470,9 +487,38 @@ class StudentLstmTrainer:
             self._set_share(self.teacher_share)
         if self._noise_seed is None:   # and so does the noise
             self._set_noise()
+        if self._faults_seed is None:   # and so do the sensor faults
+            self._set_faults()
         if actions or self._actions is not None:
             self._actions = torch.zeros(K, n, 2, **kw)
             nat.check(self._lib.rdl_envs_bind_actions(self._h, nat.ptr(self._actions), K * n), "rdl_envs_bind_actions")
+
+    # -- sensor faults on what the student reads in the envs calls ---------------------------------
+    def set_obs_faults(self, mode: str = "none", keep_prob: float = 1.0, seed: int | None = None):
+        """Mask the observations the student reads in act_envs / rollout_envs / step_envs ("student")
+        from the next call on (rdl_envs_set_obs_faults; obs_faults.py has the modes): component k of
+        record j of env i's open episode is kept iff u < keep_prob, u a function of (seed, env_base + i,
+        episode, j, k) alone, at every position of every window that holds the record -- a reading once
+        lost stays lost; "dropout" scales a kept reading by 1 / keep_prob as the training dropout does,
+        "missing" leaves it.  Only the student's pdflat, and through it (c, h) and the trajectory,
+        changes: the teacher reads the clean observation, the records and the windows (ob_w, prev_w, t_w)
+        hold the clean readings, and "teacher" calls ignore the setting.  ``seed``: the mask's key
+        (default: the envs' seed, whatever attach_envs sets it to).  "none" (the default) is the plain
+        call.  evaluate() never reads this setting.  A captured call keeps the faults it was captured
+        with."""
+        obf.native(mode, keep_prob, 0)   # ValueError before anything is kept
+        self._faults, self._faults_seed = (mode, float(keep_prob)), None if seed is None else int(seed)
+        self._set_faults()
+
+    def _set_faults(self):
+        of = obf.native(*self._faults, self._envs_seed if self._faults_seed is None else self._faults_seed)
+        nat.check(self._lib.rdl_envs_set_obs_faults(self._h, ctypes.byref(of)), "rdl_envs_set_obs_faults")
+
+    def obs_faults(self) -> dict:
+        """dict(mode, keep_prob, seed): the handle's setting (rdl_envs_obs_faults)"""
+        of = nat.RdObsFaults()
+        nat.check(self._lib.rdl_envs_obs_faults(self._h, ctypes.byref(of)), "rdl_envs_obs_faults")
+        return dict(mode=obf.MODE_NAMES[of.mode], keep_prob=float(of.keep_prob), seed=int(of.seed))
 
     # -- action noise in the envs calls ---------------------------------------------------------
     def set_action_noise(self, mode: str = "none", scale: float = 1.0, seed: int | None = None):

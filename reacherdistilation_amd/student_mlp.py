@@ -21,6 +21,7 @@ import torch
 
 from . import _native as nat
 from . import action_noise as an
+from . import obs_faults as obf
 from .config import OBSPACE_SHAPE, PDFLAT_SHAPE
 from .dist import allreduce_sum_
 from .distill import EvalResult
@@ -66,6 +67,10 @@ nat.register({
     "rdm_envs_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
     "rdm_envs_bind_actions": (INT, [P, P, I64]),
     "rdm_evaluate_noisy": (INT, [P, ctypes.POINTER(RdmEvalConfig), ctypes.POINTER(nat.RdActionNoise), P, P, P]),
+    "rdm_envs_set_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
+    "rdm_envs_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
+    "rdm_evaluate_faulty": (INT, [P, ctypes.POINTER(RdmEvalConfig), ctypes.POINTER(nat.RdObsFaults),
+                                  ctypes.POINTER(nat.RdActionNoise), P, P, P]),
     "rdm_set_teacher": (INT, [P, P, P, P]),
     "rdm_evaluate": (INT, [P, ctypes.POINTER(RdmEvalConfig), P, P, P]),
     "rdm_param_count": (INT, []),
@@ -164,6 +169,7 @@ class StudentMlpTrainer:
         self.n_envs, self.accum_steps, self._envs = 0, 0, None   # attach_envs
         self._envs_seed, self._coin_seed, self._flags = 0, None, None   # set_teacher_share, stepped_with
         self._noise, self._noise_seed, self._actions = ("none", 1.0), None, None   # set_action_noise, actions
+        self._faults, self._faults_seed = ("none", 1.0), None   # set_obs_faults
         self._grad = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdm_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdm_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed) if params is None else params)
@@ -232,7 +238,7 @@ class StudentMlpTrainer:
     def evaluate(self, n_envs: int = 4096, episodes: int = 1, *, seed: int = 0, env_base: int = 0,
                  first_episode: int = 0, draws=None, final_dist: bool = False, records: bool = False,
                  grid: int = 0, noise: str = "none", noise_scale: float = 1.0,
-                 noise_seed: int | None = None) -> EvalResult:
+                 noise_seed: int | None = None, faults=None) -> EvalResult:
         """Roll ``n_envs`` evaluation envs through ``episodes`` consecutive 50-step episodes stepped
         with this student's mean action in ONE launch (rdm_evaluate): the phase-2 loop of
         mlp_train.train(student="mlp") without the optimiser steps.  Per step the teacher set by
@@ -250,8 +256,14 @@ class StudentMlpTrainer:
         perturbed, a = mean + noise_scale (exp(logstd) | 1) xi with xi keyed (noise_seed, env_base + i,
         first_episode + e, step) -- the return under perturbed actions, bitwise the stepwise loop with
         action_noise.perturb_actions before the step.  ``noise_seed`` defaults to ``seed``.  The envs'
-        set_action_noise is never read here: the default is the noiseless return."""
+        set_action_noise is never read here: the default is the noiseless return.
+        ``faults`` = ("dropout" | "missing", keep_prob[, seed]) or a dict of them (rdm_evaluate_faulty;
+        obs_faults.py): the student reads its observation through that mask, keyed (seed, env_base + i,
+        first_episode + e, step, component) with the seed defaulting to ``seed``; the teacher and the
+        records keep the clean observation.  Composes with ``noise``.  Bitwise the stepwise loop with
+        obs_faults.mask_obs before the student's forward.  The envs' set_obs_faults is never read here."""
         nz = an.native(noise, noise_scale, seed if noise_seed is None else noise_seed)
+        of = obf.parse(faults, seed)
         n, E = int(n_envs), int(episodes)
         if n < 1 or E < 1:
             raise ValueError("n_envs >= 1 and episodes >= 1")
@@ -272,7 +284,11 @@ class StudentMlpTrainer:
         self._sync_stream()
         out = (nat.ptr(res.returns), nat.ptr(res.final_dist) if final_dist else None,
                nat.ptr(res.records) if records else None)
-        if noise == "none":
+        if of is not None:
+            nat.check(self._lib.rdm_evaluate_faulty(self._h, ctypes.byref(c), ctypes.byref(of),
+                                                    None if noise == "none" else ctypes.byref(nz), *out),
+                      "rdm_evaluate_faulty")
+        elif noise == "none":
             nat.check(self._lib.rdm_evaluate(self._h, ctypes.byref(c), *out), "rdm_evaluate")
         else:
             nat.check(self._lib.rdm_evaluate_noisy(self._h, ctypes.byref(c), ctypes.byref(nz), *out),
@@ -312,6 +328,8 @@ class StudentMlpTrainer:
             self._bind_flags()
         if self._noise_seed is None:   # the noise follows the envs' seed
             self._set_noise()
+        if self._faults_seed is None:   # and so do the sensor faults
+            self._set_faults()
         if actions or self._actions is not None:
             self._actions = torch.zeros(K, n, 2, **kw)
             nat.check(self._lib.rdm_envs_bind_actions(self._h, nat.ptr(self._actions), K * n), "rdm_envs_bind_actions")
@@ -348,6 +366,32 @@ class StudentMlpTrainer:
         rows past a shorter call's ``steps`` keep their old values.  None unless attach_envs(...,
         actions=True) asked for it."""
         return self._actions
+
+    # -- sensor faults on what the student reads in the envs calls ---------------------------------
+    def set_obs_faults(self, mode: str = "none", keep_prob: float = 1.0, seed: int | None = None):
+        """Mask the observation the student reads in act_envs / rollout_envs / step_envs ("student") from
+        the next call on (rdm_envs_set_obs_faults; obs_faults.py has the modes): component k of env i's
+        observation is kept iff u < keep_prob, u a function of (seed, env_base + i, episode, step, k)
+        alone; "dropout" scales a kept reading by 1 / keep_prob as the training dropout does, "missing"
+        leaves it.  Only the student's pdflat, and through it the trajectory, changes: the teacher reads
+        the clean observation, x and both pdflats' buffers, stepped_with, actions and the training on
+        every row are as without faults, and "teacher" calls ignore the setting.  ``seed``: the mask's
+        key (default: the envs' seed, whatever attach_envs sets it to).  "none" (the default) is the
+        plain call.  evaluate() never reads this setting.  A captured call keeps the faults it was
+        captured with."""
+        obf.native(mode, keep_prob, 0)   # ValueError before anything is kept
+        self._faults, self._faults_seed = (mode, float(keep_prob)), None if seed is None else int(seed)
+        self._set_faults()
+
+    def _set_faults(self):
+        of = obf.native(*self._faults, self._envs_seed if self._faults_seed is None else self._faults_seed)
+        nat.check(self._lib.rdm_envs_set_obs_faults(self._h, ctypes.byref(of)), "rdm_envs_set_obs_faults")
+
+    def obs_faults(self) -> dict:
+        """dict(mode, keep_prob, seed): the handle's setting (rdm_envs_obs_faults)"""
+        of = nat.RdObsFaults()
+        nat.check(self._lib.rdm_envs_obs_faults(self._h, ctypes.byref(of)), "rdm_envs_obs_faults")
+        return dict(mode=obf.MODE_NAMES[of.mode], keep_prob=float(of.keep_prob), seed=int(of.seed))
 
     # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
     def set_teacher_share(self, beta: float, seed: int | None = None):
