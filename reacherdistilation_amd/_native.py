@@ -69,6 +69,23 @@ SIGNATURES = {
     "rd_comm_check": (INT, [P]),
 }
 
+# rd?_envs_<name>: how a student's envs calls act (csrc/rd_acting.h), the same for every student's ABI
+ENVS_ACTING = {
+    "set_teacher_share": (INT, [P, F32, U64]),
+    "teacher_share": (F32, [P]),
+    "set_action_noise": (INT, [P, ctypes.POINTER(RdActionNoise)]),
+    "action_noise": (INT, [P, ctypes.POINTER(RdActionNoise)]),
+    "bind_actions": (INT, [P, P, I64]),
+    "set_obs_faults": (INT, [P, ctypes.POINTER(RdObsFaults)]),
+    "obs_faults": (INT, [P, ctypes.POINTER(RdObsFaults)]),
+}
+
+
+def envs_acting(abi: str) -> dict:
+    """ENVS_ACTING's signatures under a student's ABI prefix ("rdm", "rdl"), for register()"""
+    return {f"{abi}_envs_{name}": sig for name, sig in ENVS_ACTING.items()}
+
+
 _lib = None
 
 

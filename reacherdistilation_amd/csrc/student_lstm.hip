@@ -27,55 +27,28 @@
 // rdl_set_query_dtype's RDL_DTYPE_BF16 also sends the gate product of the closed-loop query (rdl_evaluate,
 // the envs calls) to those MFMAs (student_lstm_query_bf16.h); by default it stays f32 on the master.
 //
-// One translation unit: the device code is the ten student_lstm_*.h included below, in the order the
-// kernels stand in the object.  This file keeps rdl_trainer, the choice of launches for a batch
-// (Path), one function per cell path and head path, and the C ABI.  (The envs and evaluation kernels'
-// noisy instances, action noise, are compiled in student_lstm_noise.hip: student_lstm_noise.h; their
-// faulty instances, sensor faults on the student's observation, in student_lstm_faults.hip:
-// student_lstm_faults.h.)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// One translation unit: the device code is the eight student_lstm_*.h that student_lstm_device.h
+// includes and the two included below, in the order the kernels stand in the object.  This file keeps
+// rdl_trainer, the choice of launches for a batch (Path), one function per cell path and head path, and
+// the C ABI.  (The closed
+// loop's noisy and faulty instances -- action noise, sensor faults on the student's observation -- are
+// compiled in student_lstm_noise.hip and student_lstm_faults.hip: student_lstm_acting.h.)
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <new>
 
-#include "../../include/reacher_student_lstm.h"
-#include "rd_action_noise.h"
-#include "rd_common.h"
-#include "rd_device.h"
-#include "rd_gemm.h"
+#include "student_lstm_device.h"
+// after the ABI header, whose codes it returns
 #include "rd_host.h"
-#include "rd_obs_faults.h"
-#include "rd_physics.h"
-#include "student_lstm_faults.h"
-#include "student_lstm_noise.h"
 
 namespace {
 
-// dimensions, strides, flat parameter offsets, sigm
-#include "student_lstm_layout.h"
-// the per-step forward: inputs_kernel, cell_fwd_kernel, lstm_rec_fwd_kernel
-#include "student_lstm_step.h"
 // the persistent recurrence (at most PR_ROWS windows): lstm_fwd_persist_kernel, lstm_bptt_persist_kernel
 #include "student_lstm_persist.h"
-// the fused head: head_layer, pack_heads_kernel, head_fwd_kernel, head_bwd_kernel, grad_finish_kernel, the reduces
-#include "student_lstm_head.h"
 // cell_bwd_kernel, loss_kernel, metrics_kernel, the column sums, adam_kernel, init_ctl_kernel
 #include "student_lstm_optim.h"
-
-// one closed-loop step of a 16-env block, shared by the two below: tch::, the EV_* tiling,
-// lstm_eval_pack_kernel, the block's LDS and the ls_* pieces
-#include "student_lstm_query.h"
-// the bf16 mixed-precision cell (rdl_create_dtype's RDL_DTYPE_BF16): the Wl images and the three MFMA kernels
-#include "student_lstm_bf16.h"
-// the step's window positions on the bf16 cell (rdl_set_query_dtype): ls_positions_bf16, ls_positions_of
-#include "student_lstm_query_bf16.h"
-// the whole-episode evaluation (rdl_evaluate): student_lstm_evaluate_kernel
-#include "student_lstm_eval.h"
-// the persistent envs (rdl_envs_*, rdl_rollout_envs, rdl_step_envs): LsEnvsArgs, student_lstm_envs_kernel
-#include "student_lstm_envs.h"
 
 }  // namespace
 
@@ -117,18 +90,7 @@ struct rdl_trainer {
     float* wpart = nullptr;
     // the closed-loop query's arithmetic (rdl_set_query_dtype): RDL_DTYPE_BF16 reads wimg's forward image
     int qdtype = RDL_DTYPE_F32;
-    // DAgger's mixture in RDL_ACT_STUDENT calls (rdl_envs_set_teacher_share): host-side settings of the
-    // handle, not of its envs -- attach and reset leave them
-    float beta = 0.0f;         // the teacher's share of the env steps
-    uint64_t coin_seed = 0;
-    // action noise in the envs calls (rdl_envs_set_action_noise, rdl_envs_bind_actions): host-side
-    // settings of the handle too
-    rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
-    float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
-    int64_t action_rows = 0;
-    // sensor faults on what the student reads in RDL_ACT_STUDENT calls (rdl_envs_set_obs_faults): a
-    // host-side setting of the handle too
-    rd_obs_faults faults{RD_OBS_CLEAN, 1.0f, 0};
+    rd::Acting act;   // how the envs calls act (rdl_envs_set_*, rdl_envs_bind_actions); no stepped_with is ever bound
 };
 
 namespace {
@@ -613,10 +575,7 @@ int envs_check(const char* fn, const rdl_trainer* t, int act_with, int steps, co
                                         "of history", fn, t->T, EV_MAX_T);
     if (t->envs.n > ((int64_t)1 << 31) / steps)
         return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs.n);
-    if (t->actions && (int64_t)steps * t->envs.n > t->action_rows)
-        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the actions buffer "
-                                        "(rdl_envs_bind_actions)", fn, steps, (long long)t->envs.n,
-                             (long long)t->action_rows);
+    if (int rc = rd::check_bound_rows(fn, t->act, steps, t->envs.n)) return rc;
     if (train) {
         if (steps % rd::kEpisodeSteps)
             return rd::set_error(RD_EINVAL, "%s: steps %d is not a multiple of the episode's %d", fn, steps,
@@ -651,37 +610,21 @@ int launch_envs(rdl_trainer* t, int act_with, int steps, float* records, float* 
     const dim3 grid((unsigned)(nblk < cap ? nblk : cap)), block(EV_THREADS);
     auto* kern = !stu ? student_lstm_envs_kernel<false, false>
                  : bf16_query(t) ? student_lstm_envs_kernel<true, true> : student_lstm_envs_kernel<true, false>;
-    // sensor faults: the faulty instances for a student call (student_lstm_faults.hip); they carry the
-    // mixture and the noise too.  A teacher call evaluates no student and launches what it launched
-    if (stu && t->faults.mode != RD_OBS_CLEAN) {
-        const rd::LstmEnvsFaultLaunch l{&a, t->beta, t->coin_seed, t->noise, t->actions, t->faults, bf16_query(t), grid.x,
-                                        t->stream};
-        RD_HIP(rd::launch_lstm_envs_faulty(l), "student_lstm_envs_kernel (faulty) launch");
-        return RD_OK;
+    const rd::LstmEnvsLaunch l{&a, &t->act, stu, bf16_query(t), grid.x, block.x, t->stream};
+    switch (rd::tier_of(t->act, stu)) {
+        case rd::Tier::Faulty: RD_HIP(rd::launch_lstm_envs_faulty(l), "student_lstm_envs_kernel (faulty) launch"); break;
+        case rd::Tier::Noisy: RD_HIP(rd::launch_lstm_envs_noisy(l), "student_lstm_envs_kernel (noisy) launch"); break;
+        case rd::Tier::Mixed: {   // these instances alone live in this unit
+            auto* mixed = bf16_query(t) ? student_lstm_envs_kernel<true, true, LsEnvsMixArgs>
+                                        : student_lstm_envs_kernel<true, false, LsEnvsMixArgs>;
+            hipLaunchKernelGGL(mixed, grid, block, 0, t->stream, acting_args<LsEnvsMixArgs>(a, t->act));
+            RD_HIP(hipGetLastError(), "student_lstm_envs_kernel (mixed) launch");
+            break;
+        }
+        case rd::Tier::Plain:
+            hipLaunchKernelGGL(kern, grid, block, 0, t->stream, a);
+            RD_HIP(hipGetLastError(), "student_lstm_envs_kernel launch");
     }
-    // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
-    // wants the actions (student_lstm_noise.hip); they carry the mixture too
-    if (t->noise.mode != RD_NOISE_NONE || t->actions) {
-        const rd::LstmEnvsNoiseLaunch l{&a, stu, t->beta, t->coin_seed, t->noise, t->actions, bf16_query(t), grid.x,
-                                        t->stream};
-        RD_HIP(rd::launch_lstm_envs_noisy(l), "student_lstm_envs_kernel (noisy) launch");
-        return RD_OK;
-    }
-    // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0);
-    // otherwise the launch above, with the arguments it always had
-    if (stu && t->beta > 0.0f) {
-        LsEnvsMixArgs m{};
-        static_cast<LsEnvsArgs&>(m) = a;
-        m.beta = t->beta;
-        m.coin_seed = t->coin_seed;
-        auto* mixed = bf16_query(t) ? student_lstm_envs_kernel<true, true, true, LsEnvsMixArgs>
-                                    : student_lstm_envs_kernel<true, false, true, LsEnvsMixArgs>;
-        hipLaunchKernelGGL(mixed, grid, block, 0, t->stream, m);
-        RD_HIP(hipGetLastError(), "student_lstm_envs_kernel (mixed) launch");
-        return RD_OK;
-    }
-    hipLaunchKernelGGL(kern, grid, block, 0, t->stream, a);
-    RD_HIP(hipGetLastError(), "student_lstm_envs_kernel launch");
     return RD_OK;
 }
 
@@ -978,7 +921,7 @@ int rdl_set_teacher(rdl_trainer* t, const float* params, const float* ob_mean, c
 namespace {
 
 // rdl_evaluate (nz = of = null), rdl_evaluate_noisy (of = null) and rdl_evaluate_faulty (nz = null: the
-// mean acts), `fn` naming the caller
+// mean acts), `fn` naming the caller; the tier follows from the settings given (rd::tier_of)
 int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const rd_action_noise* nz,
              const rd_obs_faults* of, const float* state0,
              float* returns, float* final_dist, float* records, float* state_out) {
@@ -1013,20 +956,18 @@ int evaluate(const char* fn, rdl_trainer* t, const rdl_eval_config* cfg, const r
     a.T = t->T;
     // a block of 16 envs per workgroup for the whole launch, one workgroup per CU (its LDS)
     const int64_t nblk = (a.n + EV_ROWS - 1) / EV_ROWS, cap = cfg->grid > 0 ? cfg->grid : t->cus;
-    if (of) {   // the faulty instances (student_lstm_faults.hip)
-        const rd::LstmEvalFaultLaunch l{&a, nz ? *nz : rd_action_noise{RD_NOISE_NONE, 1.0f, 0}, *of, bf16_query(t),
-                                        (unsigned)(nblk < cap ? nblk : cap), t->stream};
-        RD_HIP(rd::launch_lstm_eval_faulty(l), "student_lstm_evaluate_kernel (faulty) launch");
-        return RD_OK;
-    }
-    if (nz) {   // the noisy instances (student_lstm_noise.hip)
-        const rd::LstmEvalNoiseLaunch l{&a, *nz, bf16_query(t), (unsigned)(nblk < cap ? nblk : cap), t->stream};
-        RD_HIP(rd::launch_lstm_eval_noisy(l), "student_lstm_evaluate_kernel (noisy) launch");
-        return RD_OK;
-    }
     auto* kern = bf16_query(t) ? student_lstm_evaluate_kernel<true> : student_lstm_evaluate_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(EV_THREADS), 0, t->stream, a);
-    RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
+    rd::Acting act;
+    if (nz) act.noise = *nz;
+    if (of) act.faults = *of;
+    const rd::LstmEvalLaunch l{&a, &act, bf16_query(t), (unsigned)(nblk < cap ? nblk : cap), EV_THREADS, t->stream};
+    switch (rd::tier_of(act, true)) {
+        case rd::Tier::Faulty: RD_HIP(rd::launch_lstm_eval_faulty(l), "student_lstm_evaluate_kernel (faulty) launch"); break;
+        case rd::Tier::Noisy: RD_HIP(rd::launch_lstm_eval_noisy(l), "student_lstm_evaluate_kernel (noisy) launch"); break;
+        default:
+            hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), 0, t->stream, a);
+            RD_HIP(hipGetLastError(), "student_lstm_evaluate_kernel launch");
+    }
     return RD_OK;
 }
 
@@ -1106,49 +1047,31 @@ int rdl_step_envs(rdl_trainer* t, int act_with, int steps, float* records, float
     return envs_train("rdl_step_envs", t, act_with, steps, records, reward, ob_w, prev_w, t_w, 1);
 }
 
+// how the envs calls act: the checks and the settings are rd_acting.h's
 int rdl_envs_set_teacher_share(rdl_trainer* t, float beta, uint64_t coin_seed) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_teacher_share: null trainer");
-    if (!(beta >= 0.0f && beta <= 1.0f))   // NaN too
-        return rd::set_error(RD_EINVAL, "rdl_envs_set_teacher_share: beta %g outside 0 .. 1", (double)beta);
-    t->beta = beta;
-    t->coin_seed = coin_seed;
-    return RD_OK;
+    return rd::set_teacher_share("rdl_envs_set_teacher_share", rd::acting_of(t), beta, coin_seed);
 }
 
-float rdl_envs_teacher_share(const rdl_trainer* t) { return t ? t->beta : -1.0f; }
+float rdl_envs_teacher_share(const rdl_trainer* t) { return rd::teacher_share(rd::acting_of(t)); }
 
 int rdl_envs_set_action_noise(rdl_trainer* t, const rd_action_noise* nz) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_action_noise: null trainer");
-    if (int rc = rd::check_action_noise("rdl_envs_set_action_noise", nz, true)) return rc;
-    t->noise = *nz;
-    return RD_OK;
+    return rd::set_action_noise("rdl_envs_set_action_noise", rd::acting_of(t), nz);
 }
 
 int rdl_envs_action_noise(const rdl_trainer* t, rd_action_noise* out) {
-    if (!t || !out) return rd::set_error(RD_EINVAL, "rdl_envs_action_noise: null trainer or out");
-    *out = t->noise;
-    return RD_OK;
+    return rd::get_action_noise("rdl_envs_action_noise", rd::acting_of(t), out);
 }
 
 int rdl_envs_bind_actions(rdl_trainer* t, float* buf, int64_t rows) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_bind_actions: null trainer");
-    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdl_envs_bind_actions: rows %lld < 1", (long long)rows);
-    t->actions = buf;
-    t->action_rows = buf ? rows : 0;
-    return RD_OK;
+    return rd::bind_actions("rdl_envs_bind_actions", rd::acting_of(t), buf, rows);
 }
 
 int rdl_envs_set_obs_faults(rdl_trainer* t, const rd_obs_faults* of) {
-    if (int rc = rd::check_obs_faults("rdl_envs_set_obs_faults", of, true)) return rc;
-    if (!t) return rd::set_error(RD_EINVAL, "rdl_envs_set_obs_faults: null trainer");
-    t->faults = *of;
-    return RD_OK;
+    return rd::set_obs_faults("rdl_envs_set_obs_faults", rd::acting_of(t), of);
 }
 
 int rdl_envs_obs_faults(const rdl_trainer* t, rd_obs_faults* out) {
-    if (!t || !out) return rd::set_error(RD_EINVAL, "rdl_envs_obs_faults: null trainer or out");
-    *out = t->faults;
-    return RD_OK;
+    return rd::get_obs_faults("rdl_envs_obs_faults", rd::acting_of(t), out);
 }
 
 int rdl_envs_get_state(rdl_trainer* t, float* state, int32_t* step, int32_t* episode) {

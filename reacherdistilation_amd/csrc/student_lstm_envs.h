@@ -65,16 +65,14 @@ struct LsEnvsMixArgs : LsEnvsArgs {
 };
 
 // the noisy instances' (rdl_envs_set_action_noise, rdl_envs_bind_actions), compiled in
-// student_lstm_noise.hip.  Again a struct of its own; the instances are told by it (kNoisy), so the
-// kernel's template parameters, and with them every other instance's name, stay as they are
+// student_lstm_noise.hip.  Again a struct of its own; the instances are told by it (EnvsActs), so the
+// kernel's other template parameters, and with them every other instance's name, stay as they are
 struct LsEnvsNoiseArgs : LsEnvsMixArgs {
     int32_t noise_mode;      // RD_NOISE_* (include/reacher_action_noise.h)
     float noise_scale;
     uint64_t noise_seed;     // the noise's Philox key
     float* actions;          // [K][n][2] or null: the action that stepped the env
 };
-template <class ARGS> constexpr bool kNoisy = false;
-template <> constexpr bool kNoisy<LsEnvsNoiseArgs> = true;
 
 // the faulty instances' (rdl_envs_set_obs_faults: sensor faults on the student's observation,
 // include/reacher_obs_faults.h), compiled in student_lstm_faults.hip.  Derived from the noisy one, so
@@ -84,9 +82,39 @@ struct LsEnvsFaultArgs : LsEnvsNoiseArgs {
     float obs_keep;          // keep_prob
     uint64_t obs_seed;       // the mask's Philox key
 };
-template <> constexpr bool kNoisy<LsEnvsFaultArgs> = true;
-template <class ARGS> constexpr bool kFaulty = false;
-template <> constexpr bool kFaulty<LsEnvsFaultArgs> = true;
+
+// What an instance does follows from its argument struct alone: each struct above adds its fields to
+// the one before, and an instance carries whatever its struct derives from (with the student acting,
+// for the mixture: the teacher-acting noisy instance has beta's fields and never reads them)
+template <class ARGS>
+struct EnvsActs {
+    static constexpr bool mixed = std::is_base_of_v<LsEnvsMixArgs, ARGS>;
+    static constexpr bool noisy = std::is_base_of_v<LsEnvsNoiseArgs, ARGS>;
+    static constexpr bool faulty = std::is_base_of_v<LsEnvsFaultArgs, ARGS>;
+};
+
+// ARGS for a call: the plain instance's arguments, then the fields ARGS adds from the handle's settings
+template <class ARGS>
+ARGS acting_args(const LsEnvsArgs& base, const rd::Acting& act) {
+    ARGS m{};
+    static_cast<LsEnvsArgs&>(m) = base;
+    if constexpr (EnvsActs<ARGS>::mixed) {
+        m.beta = act.beta;
+        m.coin_seed = act.coin_seed;
+    }
+    if constexpr (EnvsActs<ARGS>::noisy) {
+        m.noise_mode = act.noise.mode;
+        m.noise_scale = act.noise.scale;
+        m.noise_seed = act.noise.seed;
+        m.actions = act.actions;
+    }
+    if constexpr (EnvsActs<ARGS>::faulty) {
+        m.obs_mode = act.faults.mode;
+        m.obs_keep = act.faults.keep_prob;
+        m.obs_seed = act.faults.seed;
+    }
+    return m;
+}
 
 // episode 0 of every env; clock and aux to 0 (rd_reset's arithmetic); q and hist are memset by the host
 __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs a) {
@@ -101,12 +129,12 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
 // coin in the env's lane (rd::teacher_coin: a function of (coin seed, env, episode, step) alone, so
 // known before the step and drawn before its first barrier) that hands the teacher's T_s[0..1] to
 // env_step instead of S_s[0..1]; the record's stepped_with is 1 - coin.
-// kNoisy<ARGS> (action noise; a student instance is then MIXED too, beta = 0 never firing; the teacher
+// Acts::noisy (action noise; a student instance is then MIXED too, beta = 0 never firing; the teacher
 // instance is not): the two normal draws of this env and step in the env's lane, beside the coin
 // (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
 // T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
 // Nothing else of the step changes: the record, (c, h), the ring and the windows are the plain call's.
-// kFaulty<ARGS> (sensor faults; a student instance, MIXED and kNoisy too, either of which may be off at
+// Acts::faulty (sensor faults; a student instance, MIXED and noisy too, either of which may be off at
 // run time): columns 0..10 of the ring's x rows hold what the student READS of each record, masked by
 // the record's own (episode, step) -- the carried records at entry (the mask is a pure function, so
 // the handle's history stays clean and a call after a teacher call, a reset of the setting or a call
@@ -114,9 +142,10 @@ __global__ __launch_bounds__(256) void student_lstm_envs_reset_kernel(LsEnvsArgs
 // (ls_fault_mask, before the step's first barrier).  The clean observations live beside the ring
 // (ls_fault_clean): the windows' ob_w and the history written back come from there, the teacher's SO
 // row and the records from the clean registers.
-template <bool STUDENT_ACTS, bool BF16Q, bool MIXED = false, class ARGS = LsEnvsArgs>
+template <bool STUDENT_ACTS, bool BF16Q, class ARGS = LsEnvsArgs>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
-    static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
+    using Acts = EnvsActs<ARGS>;
+    constexpr bool MIXED = STUDENT_ACTS && Acts::mixed;   // the mixture is a student call's
     const LsThread q = ls_prologue<STUDENT_ACTS>(a.tnet, a.P, a.img, a.T);
     const int tid = q.tid, lane = q.lane, T = q.T;
     const bool phys = q.wave == 0 && lane < EV_ROWS;   // the env of this lane
@@ -133,7 +162,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             const int r = x / (T * EH_REC), y = x - r * (T * EH_REC), slot = y / EH_REC, c = y - slot * EH_REC;
             const int64_t er = row0 + r < n ? row0 + r : row0;
             const float v = a.hist[(er * T + slot) * EH_REC + c];
-            if constexpr (kFaulty<ARGS>) {
+            if constexpr (Acts::faulty) {
                 if (c < rd::kObsDim) ls_fault_clean()[slot][r][c] = v;
             }
             if (c < rd::kObsDim) lds::Xr[slot][r][c] = v;
@@ -155,7 +184,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             episode = a.clock[n + env];
         }
         __syncthreads();
-        if constexpr (kFaulty<ARGS>) {
+        if constexpr (Acts::faulty) {
             // the carried records of the open episode, as the student read them: slot's record is the last
             // j <= s - 1 with j % T = slot (none at s = 0, or where that j < 0: a stale slot no window reads)
             static_assert(STUDENT_ACTS && EV_ROWS * EV_MAX_T <= EV_THREADS, "a thread per carried record");
@@ -181,15 +210,15 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             if (phys) {   // record s, and its raw prev = T_{s-1} (zero at s = 0) into the ring
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
-                if constexpr (kNoisy<ARGS>) {
-                    if (!kFaulty<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                if constexpr (Acts::noisy) {
+                    if (!Acts::faulty || a.noise_mode != 0)   // a faulty call's noise may be off
                         ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), episode, s);
                 }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) lds::Xr[slot][lane][EH_PREV + c] = s ? lds::TO[(s - 1) & 1][lane][c] : 0.0f;
                 if constexpr (MIXED) ls_record_head(lane, slot, st, rec, carry, coin ? 0.0f : 1.0f);
                 else ls_record_head(lane, slot, st, rec, carry, STUDENT_ACTS ? 1.0f : 0.0f);
-                if constexpr (kFaulty<ARGS>)
+                if constexpr (Acts::faulty)
                     ls_fault_mask(lane, slot, a.obs_mode, a.obs_keep, a.obs_seed, (uint64_t)(a.env_base + env), episode, s,
                                   ls_fault_clean());
             }
@@ -206,7 +235,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
                     const int p = x / (EV_ROWS * rd::kObsDim), y = x - p * (EV_ROWS * rd::kObsDim);
                     const int r = y / rd::kObsDim, c = y - r * rd::kObsDim;
                     const int64_t w = wrow + r;
-                    if constexpr (kFaulty<ARGS>) {   // the clean observations
+                    if constexpr (Acts::faulty) {   // the clean observations
                         if (row0 + r < n && w < a.windows)
                             a.ob_w[((int64_t)p * a.windows + w) * rd::kObsDim + c] = ls_fault_clean()[(s - (T - 1) + p) % T][r][c];
                     } else {
@@ -230,7 +259,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
             if (phys) {
                 float sp[4];
                 ls_record_tail<STUDENT_ACTS>(lane, s, rec, tp, sp);
-                if constexpr (kNoisy<ARGS>) {
+                if constexpr (Acts::noisy) {
                     const bool tch_acts = MIXED ? coin : !STUDENT_ACTS;
                     const float xi0 = ls_noise_park()[2 * lane], xi1 = ls_noise_park()[2 * lane + 1];
                     float a0, a1;
@@ -255,7 +284,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_envs_kernel(ARGS a) {
         if (STUDENT_ACTS) ls_state_store(tid, a.q, n, row0, hp);
         for (int x = tid; x < EV_ROWS * T * EH_REC; x += EV_THREADS) {
             const int r = x / (T * EH_REC), y = x - r * (T * EH_REC), slot = y / EH_REC, c = y - slot * EH_REC;
-            if constexpr (kFaulty<ARGS>) {   // the clean observations
+            if constexpr (Acts::faulty) {   // the clean observations
                 if (row0 + r < n)
                     a.hist[((row0 + r) * T + slot) * EH_REC + c] =
                         c < rd::kObsDim ? ls_fault_clean()[slot][r][c] : c < rd::kObsDim + 4 ? lds::Xr[slot][r][EH_PREV + c - rd::kObsDim] : 0.0f;

@@ -39,8 +39,6 @@ struct LsEvalNoiseArgs : LsEvalArgs {
     float noise_scale;
     uint64_t noise_seed;
 };
-template <class ARGS> constexpr bool kNoisyEval = false;
-template <> constexpr bool kNoisyEval<LsEvalNoiseArgs> = true;
 
 // rdl_evaluate_faulty's instances (student_lstm_faults.hip): the student reads its observations through
 // the sensor faults (include/reacher_obs_faults.h) at Philox episode first_episode + e; its action may
@@ -52,9 +50,31 @@ struct LsEvalFaultArgs : LsEvalNoiseArgs {
     float obs_keep;          // keep_prob
     uint64_t obs_seed;
 };
-template <> constexpr bool kNoisyEval<LsEvalFaultArgs> = true;
-template <class ARGS> constexpr bool kFaultyEval = false;
-template <> constexpr bool kFaultyEval<LsEvalFaultArgs> = true;
+
+// What an instance does follows from its argument struct alone, as the envs kernel's EnvsActs
+template <class ARGS>
+struct EvalActs {
+    static constexpr bool noisy = std::is_base_of_v<LsEvalNoiseArgs, ARGS>;
+    static constexpr bool faulty = std::is_base_of_v<LsEvalFaultArgs, ARGS>;
+};
+
+// ARGS for a call: the plain instance's arguments, then the fields ARGS adds from the call's settings
+template <class ARGS>
+ARGS acting_args(const LsEvalArgs& base, const rd::Acting& act) {
+    ARGS m{};
+    static_cast<LsEvalArgs&>(m) = base;
+    if constexpr (EvalActs<ARGS>::noisy) {
+        m.noise_mode = act.noise.mode;
+        m.noise_scale = act.noise.scale;
+        m.noise_seed = act.noise.seed;
+    }
+    if constexpr (EvalActs<ARGS>::faulty) {
+        m.obs_mode = act.faults.mode;
+        m.obs_keep = act.faults.keep_prob;
+        m.obs_seed = act.faults.seed;
+    }
+    return m;
+}
 
 template <bool BF16Q, class ARGS = LsEvalArgs>
 __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS a) {
@@ -88,12 +108,12 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS 
             for (int s = 0; s < rd::kEpisodeSteps; ++s) {
                 const int slot = s % T;
                 float* rec = rec0 ? rec0 + s * EV_REC : nullptr;
-                if constexpr (kNoisyEval<ARGS>) {
-                    if (phys && (!kFaultyEval<ARGS> || a.noise_mode != 0))   // a faulty call's noise may be off
+                if constexpr (EvalActs<ARGS>::noisy) {
+                    if (phys && (!EvalActs<ARGS>::faulty || a.noise_mode != 0))   // a faulty call's noise may be off
                         ls_noise_draw(lane, a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s);
                 }
                 if (phys) ls_record_head(lane, slot, st, rec, carry, 1.0f);
-                if constexpr (kFaultyEval<ARGS>) {
+                if constexpr (EvalActs<ARGS>::faulty) {
                     if (phys)
                         ls_fault_mask(lane, slot, a.obs_mode, a.obs_keep, a.obs_seed, (uint64_t)(a.env_base + env),
                                       a.first_episode + e, s, nullptr);
@@ -109,7 +129,7 @@ __global__ __launch_bounds__(EV_THREADS) void student_lstm_evaluate_kernel(ARGS 
                 if (phys) {
                     float sp[4], tp[4];
                     ls_record_tail(lane, s, rec, tp, sp);
-                    if constexpr (kNoisyEval<ARGS>) {
+                    if constexpr (EvalActs<ARGS>::noisy) {
                         const float xi0 = ls_noise_park()[2 * lane], xi1 = ls_noise_park()[2 * lane + 1];
                         float a0, a1;
                         rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, sp[0], sp[1], sp[2], sp[3], a0, a1);

@@ -22,49 +22,23 @@
 //  * rdm_create_dtype(.., RDM_DTYPE_BF16, ..): the three wide layers run on v_mfma_f32_16x16x32_bf16
 //    instead (student_mlp_bf16.h), in BF = true instances of the same kernels.
 //
-// One translation unit: the device code is the eight student_mlp_*.h included below, in the order
-// the kernels stand in the object -- the closed-loop evaluation over whole episodes (rdm_evaluate)
-// in student_mlp_eval.h, the persistent envs of the batched on-policy step (rdm_step_envs) in
-// student_mlp_envs.h, their common step in student_mlp_query.h.  This file keeps rdm_trainer, the
-// choice of the row block, one launch function per kernel family, and the C ABI.  (The envs kernel's
-// mixed instances, DAgger's beta-mixture, are compiled in student_mlp_mix.hip: student_mlp_mix.h; the
-// envs and evaluation kernels' noisy instances in student_mlp_noise.hip: student_mlp_noise.h; their
-// faulty instances, sensor faults on the student's observation, in student_mlp_faults.hip:
-// student_mlp_faults.h.)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// One translation unit: the device code is the student_mlp_*.h that student_mlp_device.h includes, in
+// the order the kernels stand in the object -- the closed-loop evaluation over whole episodes
+// (rdm_evaluate) in student_mlp_eval.h, the persistent envs of the batched on-policy step
+// (rdm_step_envs) in student_mlp_envs.h, their common step in student_mlp_query.h -- and
+// student_mlp_optim.h.  This file keeps rdm_trainer, the choice of the row block, one launch function
+// per kernel family, and the C ABI.  (The closed loop's mixed, noisy and faulty instances -- DAgger's
+// beta-mixture, action noise, sensor faults on the student's observation -- are compiled in
+// student_mlp_mix.hip, student_mlp_noise.hip and student_mlp_faults.hip: student_mlp_acting.h.)
 #include <stdlib.h>
 
 #include <new>
 
-#include "../../include/reacher_student_mlp.h"
-#include "rd_action_noise.h"
-#include "rd_common.h"
-#include "rd_device.h"
+#include "student_mlp_device.h"
+// after the ABI header, whose codes it returns
 #include "rd_host.h"
-#include "rd_obs_faults.h"
-#include "rd_physics.h"
-#include "student_mlp_faults.h"
-#include "student_mlp_mix.h"
-#include "student_mlp_noise.h"
 
 namespace {
-
-using rd::f32x4, rd::mfma, rd::ld4, rd::wave_sum, rd::tanh_fast, rd::fence_begin, rd::fence_end;
-
-// dimensions, the flat / workspace / image layouts, pk, the LDS buffers of a row block, Part
-#include "student_mlp_layout.h"
-// the layer templates, their bf16 siblings (student_mlp_bf16.h) and the fwd / dgrad / wgrad selectors
-#include "student_mlp_layers.h"
-// the forward and the training step: SmArgs, student_mlp_kernel
-#include "student_mlp_train.h"
-
-// one closed-loop step of a block of envs, shared by the two below: tch::, EREC, ELay, the qs_* pieces
-#include "student_mlp_query.h"
-// the whole-episode evaluation (rdm_evaluate): SmEvalArgs, student_mlp_evaluate_kernel
-#include "student_mlp_eval.h"
-// the persistent envs (rdm_envs_*, rdm_step_envs): SmEnvsArgs, student_mlp_envs_kernel
-#include "student_mlp_envs.h"
 
 // PIdx, param_index, store_param, pack_kernel, reduce_adam_kernel, init_ctl_kernel
 #include "student_mlp_optim.h"
@@ -92,20 +66,7 @@ struct rdm_trainer {
     float* tnet = nullptr;      // rdm_evaluate's teacher: params [tch::P_TOT] | ob mean [11] | ob std [11]
     bool has_teacher = false;
     rd::EnvBufs envs;           // the persistent envs (rdm_envs_attach): state [8][n], aux [ENV_AUX][n], clock
-    // DAgger's mixture in RDM_ACT_STUDENT calls (rdm_envs_set_teacher_share, rdm_envs_bind_stepped_with):
-    // host-side settings of the handle, not of its envs -- attach and reset leave them
-    float beta = 0.0f;          // the teacher's share of the env steps
-    uint64_t coin_seed = 0;
-    float* flags = nullptr;     // the caller's stepped_with buffer [flag_rows], or null
-    int64_t flag_rows = 0;
-    // action noise in the envs calls (rdm_envs_set_action_noise, rdm_envs_bind_actions): host-side
-    // settings of the handle too
-    rd_action_noise noise{RD_NOISE_NONE, 1.0f, 0};
-    float* actions = nullptr;   // the caller's buffer [action_rows][2] of the actions that stepped, or null
-    int64_t action_rows = 0;
-    // sensor faults on what the student reads in RDM_ACT_STUDENT calls (rdm_envs_set_obs_faults): a
-    // host-side setting of the handle too
-    rd_obs_faults faults{RD_OBS_CLEAN, 1.0f, 0};
+    rd::Acting act;             // how the envs calls act (rdm_envs_set_*, rdm_envs_bind_*)
 };
 
 namespace {
@@ -239,15 +200,7 @@ int envs_check(const char* fn, const rdm_trainer* t, int act_with, int steps, co
     if (t->envs.n > ((int64_t)1 << 31) / steps)
         return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld rows > 2^31", fn, steps, (long long)t->envs.n);
     if (!t->has_teacher) return rd::set_error(RD_EINVAL, "%s: no teacher set (rdm_set_teacher)", fn);
-    if (t->flags && (int64_t)steps * t->envs.n > t->flag_rows)
-        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the stepped_with buffer "
-                                        "(rdm_envs_bind_stepped_with)", fn, steps, (long long)t->envs.n,
-                             (long long)t->flag_rows);
-    if (t->actions && (int64_t)steps * t->envs.n > t->action_rows)
-        return rd::set_error(RD_EINVAL, "%s: steps x n_envs = %d x %lld > rows = %lld of the actions buffer "
-                                        "(rdm_envs_bind_actions)", fn, steps, (long long)t->envs.n,
-                             (long long)t->action_rows);
-    return RD_OK;
+    return rd::check_bound_rows(fn, t->act, steps, t->envs.n);
 }
 
 // K env steps of every env: a block of envs per workgroup for the whole launch, sized as rdm_evaluate's
@@ -264,37 +217,18 @@ int launch_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pdfl
     auto* kern = stu && t->bf ? (b.small ? student_mlp_envs_kernel<16, true, true> : student_mlp_envs_kernel<64, true, true>)
                  : b.small    ? (stu ? student_mlp_envs_kernel<16, true, false> : student_mlp_envs_kernel<16, false, false>)
                               : (stu ? student_mlp_envs_kernel<64, true, false> : student_mlp_envs_kernel<64, false, false>);
-    // sensor faults: the faulty instances for a student call (student_mlp_faults.hip); they carry the
-    // mixture and the noise too.  A teacher call evaluates no student and launches what it launched
-    if (stu && t->faults.mode != RD_OBS_CLEAN) {
-        const rd::MlpEnvsFaultLaunch l{&a, t->beta, t->coin_seed, t->flags, t->noise, t->actions, t->faults, t->bf,
-                                       b.small, b.grid, b.threads, t->stream};
-        RD_HIP(rd::launch_mlp_envs_faulty(l), "student_mlp_envs_kernel (faulty) launch");
-        return RD_OK;
-    }
-    // action noise: the noisy instances, of either actor, once a noise is set or an actions buffer
-    // wants the actions (student_mlp_noise.hip); they carry the mixture too
-    if (t->noise.mode != RD_NOISE_NONE || t->actions) {
-        if (!stu && t->flags)   // the teacher stepped every row
-            RD_HIP(hipMemsetAsync(t->flags, 0, sizeof(float) * (size_t)steps * (size_t)a.n, t->stream),
-                   "student_mlp_envs_kernel: stepped_with");
-        const rd::MlpEnvsNoiseLaunch l{&a, stu, t->beta, t->coin_seed, t->flags, t->noise, t->actions, t->bf, b.small,
-                                       b.grid, b.threads, t->stream};
-        RD_HIP(rd::launch_mlp_envs_noisy(l), "student_mlp_envs_kernel (noisy) launch");
-        return RD_OK;
-    }
-    // DAgger's mixture: the mixed instances for a student call once a coin can fall (beta > 0) or a
-    // stepped_with buffer wants its flags; otherwise the launch above, with the arguments it always had
-    if (stu && (t->beta > 0.0f || t->flags)) {
-        const rd::MlpEnvsMixLaunch l{&a, t->beta, t->coin_seed, t->flags, t->bf, b.small, b.grid, b.threads, t->stream};
-        RD_HIP(rd::launch_mlp_envs_mixed(l), "student_mlp_envs_kernel (mixed) launch");   // student_mlp_mix.hip
-        return RD_OK;
-    }
-    if (t->flags)   // the teacher stepped every row
-        RD_HIP(hipMemsetAsync(t->flags, 0, sizeof(float) * (size_t)steps * (size_t)a.n, t->stream),
+    if (!stu && t->act.stepped_with)   // the teacher stepped every row
+        RD_HIP(hipMemsetAsync(t->act.stepped_with, 0, sizeof(float) * (size_t)steps * (size_t)a.n, t->stream),
                "student_mlp_envs_kernel: stepped_with");
-    hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
-    RD_HIP(hipGetLastError(), "student_mlp_envs_kernel launch");
+    const rd::MlpEnvsLaunch l{&a, &t->act, stu, t->bf, b.small, b.grid, b.threads, t->stream};
+    switch (rd::tier_of(t->act, stu)) {
+        case rd::Tier::Faulty: RD_HIP(rd::launch_mlp_envs_faulty(l), "student_mlp_envs_kernel (faulty) launch"); break;
+        case rd::Tier::Noisy: RD_HIP(rd::launch_mlp_envs_noisy(l), "student_mlp_envs_kernel (noisy) launch"); break;
+        case rd::Tier::Mixed: RD_HIP(rd::launch_mlp_envs_mixed(l), "student_mlp_envs_kernel (mixed) launch"); break;
+        case rd::Tier::Plain:
+            hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
+            RD_HIP(hipGetLastError(), "student_mlp_envs_kernel launch");
+    }
     return RD_OK;
 }
 
@@ -487,7 +421,7 @@ int rdm_set_teacher(rdm_trainer* t, const float* params, const float* ob_mean, c
 namespace {
 
 // rdm_evaluate (nz = of = null), rdm_evaluate_noisy (of = null) and rdm_evaluate_faulty (nz = null: the
-// mean acts), `fn` naming the caller
+// mean acts), `fn` naming the caller; the tier follows from the settings given (rd::tier_of)
 int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const rd_action_noise* nz,
              const rd_obs_faults* of, float* returns, float* final_dist, float* records) {
     if (!t || !cfg || !returns) return rd::set_error(RD_EINVAL, "%s: null trainer, config or returns", fn);
@@ -513,21 +447,19 @@ int evaluate(const char* fn, rdm_trainer* t, const rdm_eval_config* cfg, const r
     a.first_episode = cfg->first_episode;
     // a block of envs per workgroup for the whole launch, sized as rdm_forward sizes its row block
     const Blocks b = blocks_of(a.n, cfg->grid > 0 ? cfg->grid : t->grid, eval_small_rows, true);
-    if (of) {   // the faulty instances (student_mlp_faults.hip)
-        const rd::MlpEvalFaultLaunch l{&a, nz ? *nz : rd_action_noise{RD_NOISE_NONE, 1.0f, 0}, *of, t->bf, b.small,
-                                       b.grid, b.threads, t->stream};
-        RD_HIP(rd::launch_mlp_eval_faulty(l), "student_mlp_evaluate_kernel (faulty) launch");
-        return RD_OK;
-    }
-    if (nz) {   // the noisy instances (student_mlp_noise.hip)
-        const rd::MlpEvalNoiseLaunch l{&a, *nz, t->bf, b.small, b.grid, b.threads, t->stream};
-        RD_HIP(rd::launch_mlp_eval_noisy(l), "student_mlp_evaluate_kernel (noisy) launch");
-        return RD_OK;
-    }
     auto* kern = t->bf ? (b.small ? student_mlp_evaluate_kernel<16, true> : student_mlp_evaluate_kernel<64, true>)
                        : (b.small ? student_mlp_evaluate_kernel<16, false> : student_mlp_evaluate_kernel<64, false>);
-    hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
-    RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
+    rd::Acting act;
+    if (nz) act.noise = *nz;
+    if (of) act.faults = *of;
+    const rd::MlpEvalLaunch l{&a, &act, t->bf, b.small, b.grid, b.threads, t->stream};
+    switch (rd::tier_of(act, true)) {
+        case rd::Tier::Faulty: RD_HIP(rd::launch_mlp_eval_faulty(l), "student_mlp_evaluate_kernel (faulty) launch"); break;
+        case rd::Tier::Noisy: RD_HIP(rd::launch_mlp_eval_noisy(l), "student_mlp_evaluate_kernel (noisy) launch"); break;
+        default:
+            hipLaunchKernelGGL(kern, dim3(b.grid), dim3(b.threads), 0, t->stream, a);
+            RD_HIP(hipGetLastError(), "student_mlp_evaluate_kernel launch");
+    }
     return RD_OK;
 }
 
@@ -597,57 +529,35 @@ int rdm_step_envs(rdm_trainer* t, int act_with, int steps, float* x, float* t_pd
     return envs_train("rdm_step_envs", t, act_with, steps, x, t_pdflat, s_pdflat, reward, 1);
 }
 
+// how the envs calls act: the checks and the settings are rd_acting.h's
 int rdm_envs_set_teacher_share(rdm_trainer* t, float beta, uint64_t coin_seed) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_teacher_share: null trainer");
-    if (!(beta >= 0.0f && beta <= 1.0f))   // NaN too
-        return rd::set_error(RD_EINVAL, "rdm_envs_set_teacher_share: beta %g outside 0 .. 1", (double)beta);
-    t->beta = beta;
-    t->coin_seed = coin_seed;
-    return RD_OK;
+    return rd::set_teacher_share("rdm_envs_set_teacher_share", rd::acting_of(t), beta, coin_seed);
 }
 
-float rdm_envs_teacher_share(const rdm_trainer* t) { return t ? t->beta : -1.0f; }
+float rdm_envs_teacher_share(const rdm_trainer* t) { return rd::teacher_share(rd::acting_of(t)); }
 
 int rdm_envs_bind_stepped_with(rdm_trainer* t, float* buf, int64_t rows) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_bind_stepped_with: null trainer");
-    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_stepped_with: rows %lld < 1", (long long)rows);
-    t->flags = buf;
-    t->flag_rows = buf ? rows : 0;
-    return RD_OK;
+    return rd::bind_stepped_with("rdm_envs_bind_stepped_with", rd::acting_of(t), buf, rows);
 }
 
 int rdm_envs_set_action_noise(rdm_trainer* t, const rd_action_noise* nz) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_action_noise: null trainer");
-    if (int rc = rd::check_action_noise("rdm_envs_set_action_noise", nz, true)) return rc;
-    t->noise = *nz;
-    return RD_OK;
+    return rd::set_action_noise("rdm_envs_set_action_noise", rd::acting_of(t), nz);
 }
 
 int rdm_envs_action_noise(const rdm_trainer* t, rd_action_noise* out) {
-    if (!t || !out) return rd::set_error(RD_EINVAL, "rdm_envs_action_noise: null trainer or out");
-    *out = t->noise;
-    return RD_OK;
+    return rd::get_action_noise("rdm_envs_action_noise", rd::acting_of(t), out);
 }
 
 int rdm_envs_bind_actions(rdm_trainer* t, float* buf, int64_t rows) {
-    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_bind_actions: null trainer");
-    if (buf && rows < 1) return rd::set_error(RD_EINVAL, "rdm_envs_bind_actions: rows %lld < 1", (long long)rows);
-    t->actions = buf;
-    t->action_rows = buf ? rows : 0;
-    return RD_OK;
+    return rd::bind_actions("rdm_envs_bind_actions", rd::acting_of(t), buf, rows);
 }
 
 int rdm_envs_set_obs_faults(rdm_trainer* t, const rd_obs_faults* of) {
-    if (int rc = rd::check_obs_faults("rdm_envs_set_obs_faults", of, true)) return rc;
-    if (!t) return rd::set_error(RD_EINVAL, "rdm_envs_set_obs_faults: null trainer");
-    t->faults = *of;
-    return RD_OK;
+    return rd::set_obs_faults("rdm_envs_set_obs_faults", rd::acting_of(t), of);
 }
 
 int rdm_envs_obs_faults(const rdm_trainer* t, rd_obs_faults* out) {
-    if (!t || !out) return rd::set_error(RD_EINVAL, "rdm_envs_obs_faults: null trainer or out");
-    *out = t->faults;
-    return RD_OK;
+    return rd::get_obs_faults("rdm_envs_obs_faults", rd::acting_of(t), out);
 }
 
 int rdm_envs_get_state(rdm_trainer* t, float* state, int32_t* step, int32_t* episode) {

@@ -47,16 +47,14 @@ struct SmEnvsMixArgs : SmEnvsArgs {
 };
 
 // the noisy instances' (rdm_envs_set_action_noise, rdm_envs_bind_actions), compiled in
-// student_mlp_noise.hip.  Again a struct of its own; the instances are told by it (kNoisy), so the
-// kernel's template parameters, and with them every other instance's name, stay as they are
+// student_mlp_noise.hip.  Again a struct of its own; the instances are told by it (EnvsActs), so the
+// kernel's other template parameters, and with them every other instance's name, stay as they are
 struct SmEnvsNoiseArgs : SmEnvsMixArgs {
     int32_t noise_mode;      // RD_NOISE_* (include/reacher_action_noise.h)
     float noise_scale;
     uint64_t noise_seed;     // the noise's Philox key
     float* actions;          // [K][n][2] or null: the action that stepped the env
 };
-template <class ARGS> constexpr bool kNoisy = false;
-template <> constexpr bool kNoisy<SmEnvsNoiseArgs> = true;
 
 // the faulty instances' (rdm_envs_set_obs_faults: sensor faults on the student's observation,
 // include/reacher_obs_faults.h), compiled in student_mlp_faults.hip.  Derived from the noisy one, so
@@ -66,9 +64,40 @@ struct SmEnvsFaultArgs : SmEnvsNoiseArgs {
     float obs_keep;          // keep_prob
     uint64_t obs_seed;       // the mask's Philox key
 };
-template <> constexpr bool kNoisy<SmEnvsFaultArgs> = true;
-template <class ARGS> constexpr bool kFaulty = false;
-template <> constexpr bool kFaulty<SmEnvsFaultArgs> = true;
+
+// What an instance does follows from its argument struct alone: each struct above adds its fields to
+// the one before, and an instance carries whatever its struct derives from (with the student acting,
+// for the mixture: the teacher-acting noisy instance has beta's fields and never reads them)
+template <class ARGS>
+struct EnvsActs {
+    static constexpr bool mixed = std::is_base_of_v<SmEnvsMixArgs, ARGS>;
+    static constexpr bool noisy = std::is_base_of_v<SmEnvsNoiseArgs, ARGS>;
+    static constexpr bool faulty = std::is_base_of_v<SmEnvsFaultArgs, ARGS>;
+};
+
+// ARGS for a call: the plain instance's arguments, then the fields ARGS adds from the handle's settings
+template <class ARGS>
+ARGS acting_args(const SmEnvsArgs& base, const rd::Acting& act) {
+    ARGS m{};
+    static_cast<SmEnvsArgs&>(m) = base;
+    if constexpr (EnvsActs<ARGS>::mixed) {
+        m.beta = act.beta;
+        m.coin_seed = act.coin_seed;
+        m.stepped_with = act.stepped_with;
+    }
+    if constexpr (EnvsActs<ARGS>::noisy) {
+        m.noise_mode = act.noise.mode;
+        m.noise_scale = act.noise.scale;
+        m.noise_seed = act.noise.seed;
+        m.actions = act.actions;
+    }
+    if constexpr (EnvsActs<ARGS>::faulty) {
+        m.obs_mode = act.faults.mode;
+        m.obs_keep = act.faults.keep_prob;
+        m.obs_seed = act.faults.seed;
+    }
+    return m;
+}
 
 // episode 0 of every env; clocks, carried reward and previous fields to 0 (rd_reset's arithmetic)
 __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs a) {
@@ -85,28 +114,29 @@ __global__ __launch_bounds__(256) void student_mlp_envs_reset_kernel(SmEnvsArgs 
 // (coin seed, env, episode, step) alone, drawn before the step's first barrier so that it runs beside
 // the layers -- that hands the teacher's T_s[0..1] to env_step instead of S_s[0..1].  x, t_pdflat and
 // s_pdflat are written as the student instance writes them; the coin goes to stepped_with.
-// kNoisy<ARGS> (action noise; a student instance is then MIXED too, beta = 0 never firing; a teacher
+// Acts::noisy (action noise; a student instance is then MIXED too, beta = 0 never firing; a teacher
 // instance is not): the two normal draws of this env and step in the env's lane, beside the coin
 // (rd::action_noise_draw), and env_step takes rd::action_noise_apply of them and the acting pdflat --
 // T_s where the teacher acts, S_s else -- instead of its mean; that action goes to `actions`.
 // Nothing else of the step changes.
-// kFaulty<ARGS> (sensor faults; a student instance, MIXED and kNoisy too, either of which may be off at
+// Acts::faulty (sensor faults; a student instance, MIXED and noisy too, either of which may be off at
 // run time): the env's lane draws this record's keep bits beside the coin and the noise
 // (rd::obs_fault_keep, three Philox calls before the step's first barrier) and overwrites the
 // observation part of its X0 row with rd::obs_fault_see of them.  Only the student's layer 0 reads X0:
 // the teacher's SO row, x and every other output keep the clean registers.
-template <int ROWS, bool STUDENT_ACTS, bool BF, bool MIXED = false, class ARGS = SmEnvsArgs>
+template <int ROWS, bool STUDENT_ACTS, bool BF, class ARGS = SmEnvsArgs>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(ARGS a) {
     // MIXED: the teacher steps this lane's env now.  The kernel's first local: declared inside the step
     // loop it moves hipcc's layout of the six instances that never read it
     // (profiles/envs_teacher_share_isa.txt)
     bool coin = false;
-    float xi0 = 0.0f, xi1 = 0.0f;   // kNoisy: this step's draws, declared here for the same reason
+    float xi0 = 0.0f, xi1 = 0.0f;   // Acts::noisy: this step's draws, declared here for the same reason
     __shared__ __attribute__((aligned(16))) float lds[ELay<ROWS>::LDS_FLOATS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
     tch::load_net(lds + ELay<ROWS>::O_NET, a.tnet, false, ELay<ROWS>::THREADS);   // published by the first step's barriers
     const bool phys = wave == 0 && lane < ROWS;   // the env of this lane
-    static_assert(STUDENT_ACTS || !MIXED, "the mixture is a student call's");
+    using Acts = EnvsActs<ARGS>;
+    constexpr bool MIXED = STUDENT_ACTS && Acts::mixed;   // the mixture is a student call's
     const int64_t n = a.n, nblk = (n + ROWS - 1) / ROWS;
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int64_t row0 = blk * ROWS;
@@ -131,13 +161,13 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(A
             if (phys) {
                 if constexpr (MIXED)
                     coin = rd::teacher_coin(a.coin_seed, (uint64_t)(a.env_base + env), episode, s, a.beta);
-                if constexpr (kNoisy<ARGS>) {
-                    if (!kFaulty<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                if constexpr (Acts::noisy) {
+                    if (!Acts::faulty || a.noise_mode != 0)   // a faulty call's noise may be off
                         rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), episode, s, xi0, xi1);
                 }
                 float row[RDM_IN];
                 qs_row<ROWS, STUDENT_ACTS>(lds, lane, st, s, tp, prev_field, row);
-                if constexpr (kFaulty<ARGS>) {
+                if constexpr (Acts::faulty) {
                     static_assert(STUDENT_ACTS, "the faults are on what the student reads");
                     const uint32_t keep = rd::obs_fault_keep(a.obs_seed, (uint64_t)(a.env_base + env), episode, s, a.obs_keep);
                     float* X0 = lds + Lay<ROWS>::O_X0;
@@ -157,7 +187,7 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_envs_kernel(A
             if (phys) {
                 float sp[RDM_OUT];
                 qs_outputs<ROWS, STUDENT_ACTS>(lds, lane, sp, tp);
-                if constexpr (kNoisy<ARGS>) {
+                if constexpr (Acts::noisy) {
                     const bool tch_acts = MIXED ? coin : !STUDENT_ACTS;
                     float a0, a1;
                     rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, tch_acts ? tp[0] : sp[0],

@@ -31,8 +31,6 @@ struct SmEvalNoiseArgs : SmEvalArgs {
     float noise_scale;
     uint64_t noise_seed;
 };
-template <class ARGS> constexpr bool kNoisyEval = false;
-template <> constexpr bool kNoisyEval<SmEvalNoiseArgs> = true;
 
 // rdm_evaluate_faulty's instances (student_mlp_faults.hip): the student reads its observation through
 // the sensor faults (include/reacher_obs_faults.h) at Philox episode first_episode + e; its action may
@@ -44,13 +42,35 @@ struct SmEvalFaultArgs : SmEvalNoiseArgs {
     float obs_keep;          // keep_prob
     uint64_t obs_seed;
 };
-template <> constexpr bool kNoisyEval<SmEvalFaultArgs> = true;
-template <class ARGS> constexpr bool kFaultyEval = false;
-template <> constexpr bool kFaultyEval<SmEvalFaultArgs> = true;
+
+// What an instance does follows from its argument struct alone, as the envs kernel's EnvsActs
+template <class ARGS>
+struct EvalActs {
+    static constexpr bool noisy = std::is_base_of_v<SmEvalNoiseArgs, ARGS>;
+    static constexpr bool faulty = std::is_base_of_v<SmEvalFaultArgs, ARGS>;
+};
+
+// ARGS for a call: the plain instance's arguments, then the fields ARGS adds from the call's settings
+template <class ARGS>
+ARGS acting_args(const SmEvalArgs& base, const rd::Acting& act) {
+    ARGS m{};
+    static_cast<SmEvalArgs&>(m) = base;
+    if constexpr (EvalActs<ARGS>::noisy) {
+        m.noise_mode = act.noise.mode;
+        m.noise_scale = act.noise.scale;
+        m.noise_seed = act.noise.seed;
+    }
+    if constexpr (EvalActs<ARGS>::faulty) {
+        m.obs_mode = act.faults.mode;
+        m.obs_keep = act.faults.keep_prob;
+        m.obs_seed = act.faults.seed;
+    }
+    return m;
+}
 
 template <int ROWS, bool BF, class ARGS = SmEvalArgs>
 __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kernel(ARGS a) {
-    // kNoisyEval: the step's draws.  The kernel's first locals, as student_mlp_envs_kernel's coin is:
+    // EvalActs::noisy: the step's draws.  The kernel's first locals, as student_mlp_envs_kernel's coin is:
     // declared inside the step loop they move hipcc's register names in the four plain instances
     float xi0 = 0.0f, xi1 = 0.0f;
     __shared__ __attribute__((aligned(16))) float lds[ELay<ROWS>::LDS_FLOATS];
@@ -80,13 +100,13 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
             float* rec = a.records && valid ? a.records + ((int64_t)e * n + env) * (rd::kEpisodeSteps * EREC) : nullptr;
             for (int s = 0; s < rd::kEpisodeSteps; ++s) {
                 if (phys) {
-                    if constexpr (kNoisyEval<ARGS>) {
-                        if (!kFaultyEval<ARGS> || a.noise_mode != 0)   // a faulty call's noise may be off
+                    if constexpr (EvalActs<ARGS>::noisy) {
+                        if (!EvalActs<ARGS>::faulty || a.noise_mode != 0)   // a faulty call's noise may be off
                             rd::action_noise_draw(a.noise_seed, (uint64_t)(a.env_base + env), a.first_episode + e, s, xi0, xi1);
                     }
                     float row[RDM_IN];
                     qs_row<ROWS, true>(lds, lane, st, s, tp, prev_field, row);
-                    if constexpr (kFaultyEval<ARGS>) {
+                    if constexpr (EvalActs<ARGS>::faulty) {
                         const uint32_t keep = rd::obs_fault_keep(a.obs_seed, (uint64_t)(a.env_base + env),
                                                                  a.first_episode + e, s, a.obs_keep);
                         float* X0 = lds + Lay<ROWS>::O_X0;
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                 }
                 // (the noisy instances run layer 1 fenced, as the envs kernel does: unfenced, the 64-env f32
                 // one had the loads into an in-flight MFMA's SrcC that student_mlp_envs.h describes)
-                qs_layers<ROWS, true, BF, kNoisyEval<ARGS>>(lds, a.img, wave, i, g);
+                qs_layers<ROWS, true, BF, EvalActs<ARGS>::noisy>(lds, a.img, wave, i, g);
                 if (phys) {
                     float sp[RDM_OUT];
                     qs_outputs<ROWS, true>(lds, lane, sp, tp);
@@ -117,7 +137,7 @@ __global__ __launch_bounds__(ELay<ROWS>::THREADS) void student_mlp_evaluate_kern
                             r[RDM_OUT + c] = sp[c];
                         }
                     }
-                    if constexpr (kNoisyEval<ARGS>) {
+                    if constexpr (EvalActs<ARGS>::noisy) {
                         float a0, a1;
                         rd::action_noise_apply(a.noise_mode, a.noise_scale, xi0, xi1, sp[0], sp[1], sp[2], sp[3], a0, a1);
                         carry = rd::env_step<true>(st, a0, a1);

@@ -31,6 +31,7 @@ import torch
 from . import _native as nat
 from . import action_noise as an
 from . import obs_faults as obf
+from ._envs_acting import EnvsActing
 from .config import LSTM_BATCH_SIZE, NUM_UNITS, OBSPACE_SHAPE, PDFLAT_SHAPE, STEPS_UNROLLED
 from .dist import allreduce_sum_
 from .distill import EvalResult
@@ -87,13 +88,7 @@ nat.register({
     "rdl_step_envs": _ENVS_TRAIN,
     "rdl_envs_get_state": (INT, [P, P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "rdl_envs_get_query_state": (INT, [P, P]),
-    "rdl_envs_set_teacher_share": (INT, [P, F32, U64]),
-    "rdl_envs_teacher_share": (F32, [P]),
-    "rdl_envs_set_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
-    "rdl_envs_action_noise": (INT, [P, ctypes.POINTER(nat.RdActionNoise)]),
-    "rdl_envs_bind_actions": (INT, [P, P, I64]),
-    "rdl_envs_set_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
-    "rdl_envs_obs_faults": (INT, [P, ctypes.POINTER(nat.RdObsFaults)]),
+    **nat.envs_acting("rdl"),
     "rdl_evaluate_faulty": (INT, [P, ctypes.POINTER(RdlEvalConfig), ctypes.POINTER(nat.RdObsFaults),
                                   ctypes.POINTER(nat.RdActionNoise), P, P, P, P, P]),
     "rdl_evaluate_noisy": (INT, [P, ctypes.POINTER(RdlEvalConfig), ctypes.POINTER(nat.RdActionNoise), P, P, P, P, P]),
@@ -198,7 +193,9 @@ def query_dtype_of(name, dtype: str) -> int:
     return DTYPES[name]
 
 
-class StudentLstmTrainer:
+class StudentLstmTrainer(EnvsActing):
+    _ABI = "rdl"
+
     def __init__(self, cfg: StudentLstmConfig | None = None, device="cuda:0", rank: int = 0, world_size: int = 1,
                  process_group=None, params=None, row_base: int = 0):
         self.cfg = cfg or StudentLstmConfig()
@@ -225,9 +222,7 @@ class StudentLstmTrainer:
         nat.check(self._lib.rdl_set_query_dtype(self._h, qdtype), "rdl_set_query_dtype")
         self.teacher = None   # evaluate()'s teacher (set_teacher)
         self._envs = None     # attach_envs()'s buffers
-        self._envs_seed, self._coin_seed = 0, None   # set_teacher_share
-        self._noise, self._noise_seed, self._actions = ("none", 1.0), None, None   # set_action_noise, actions
-        self._faults, self._faults_seed = ("none", 1.0), None   # set_obs_faults
+        self._init_acting()
         self._grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         nat.check(self._lib.rdl_bind_grad_buffer(self._h, nat.ptr(self._grad)), "rdl_bind_grad_buffer")
         self.set_params(glorot_init(self.cfg.init_seed, self.T) if params is None else params)
@@ -482,101 +477,25 @@ class StudentLstmTrainer:
                                 torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None,
                                 torch.zeros(T * Bm * PDFLAT_SHAPE, **kw) if Bm else None)
         self.n_envs, self.accum_steps = n, K
-        self._envs_seed = int(seed)
-        if self._coin_seed is None:   # the coins follow the envs' seed
-            self._set_share(self.teacher_share)
-        if self._noise_seed is None:   # and so does the noise
-            self._set_noise()
-        if self._faults_seed is None:   # and so do the sensor faults
-            self._set_faults()
-        if actions or self._actions is not None:
-            self._actions = torch.zeros(K, n, 2, **kw)
-            nat.check(self._lib.rdl_envs_bind_actions(self._h, nat.ptr(self._actions), K * n), "rdl_envs_bind_actions")
+        self._attach_acting(seed, K, n, actions)
 
-    # -- sensor faults on what the student reads in the envs calls ---------------------------------
+    # -- how the envs calls act: EnvsActing's settings, and what each leaves unchanged here ---------
     def set_obs_faults(self, mode: str = "none", keep_prob: float = 1.0, seed: int | None = None):
-        """Mask the observations the student reads in act_envs / rollout_envs / step_envs ("student")
-        from the next call on (rdl_envs_set_obs_faults; obs_faults.py has the modes): component k of
-        record j of env i's open episode is kept iff u < keep_prob, u a function of (seed, env_base + i,
-        episode, j, k) alone, at every position of every window that holds the record -- a reading once
-        lost stays lost; "dropout" scales a kept reading by 1 / keep_prob as the training dropout does,
-        "missing" leaves it.  Only the student's pdflat, and through it (c, h) and the trajectory,
-        changes: the teacher reads the clean observation, the records and the windows (ob_w, prev_w, t_w)
-        hold the clean readings, and "teacher" calls ignore the setting.  ``seed``: the mask's key
-        (default: the envs' seed, whatever attach_envs sets it to).  "none" (the default) is the plain
-        call.  evaluate() never reads this setting.  A captured call keeps the faults it was captured
-        with."""
-        obf.native(mode, keep_prob, 0)   # ValueError before anything is kept
-        self._faults, self._faults_seed = (mode, float(keep_prob)), None if seed is None else int(seed)
-        self._set_faults()
+        """EnvsActing.set_obs_faults, on the records of the window: component k of record j of env i's open
+        episode is masked by (seed, env_base + i, episode, j, k) at every position of every window that
+        holds the record -- a reading once lost stays lost.  Through the student's pdflat (c, h) changes
+        too; the records and the windows (ob_w, prev_w, t_w) hold the clean readings."""
+        EnvsActing.set_obs_faults(self, mode, keep_prob, seed)
 
-    def _set_faults(self):
-        of = obf.native(*self._faults, self._envs_seed if self._faults_seed is None else self._faults_seed)
-        nat.check(self._lib.rdl_envs_set_obs_faults(self._h, ctypes.byref(of)), "rdl_envs_set_obs_faults")
-
-    def obs_faults(self) -> dict:
-        """dict(mode, keep_prob, seed): the handle's setting (rdl_envs_obs_faults)"""
-        of = nat.RdObsFaults()
-        nat.check(self._lib.rdl_envs_obs_faults(self._h, ctypes.byref(of)), "rdl_envs_obs_faults")
-        return dict(mode=obf.MODE_NAMES[of.mode], keep_prob=float(of.keep_prob), seed=int(of.seed))
-
-    # -- action noise in the envs calls ---------------------------------------------------------
     def set_action_noise(self, mode: str = "none", scale: float = 1.0, seed: int | None = None):
-        """Sample the acting policy in act_envs / rollout_envs / step_envs from the next call on
-        (rdl_envs_set_action_noise; action_noise.py has the modes), under "student" (with the teacher
-        share's coin as it is) and under "teacher" (DART's noisy expert): the action handed to env.step
-        is mean + scale (exp(logstd) | 1) xi of whoever acts at that step, xi a function of (seed,
-        env_base + i, episode, step) alone.  Only that action changes: the records, (c, h), the ring, the
-        windows and the training on every window are as without noise.  ``seed``: the noise's key
-        (default: the envs' seed, whatever attach_envs sets it to).  "none" (the default) is the plain
-        call.  evaluate() never reads this setting.  A captured call keeps the noise it was captured
-        with."""
-        an.native(mode, scale, 0)   # ValueError before anything is kept
-        self._noise, self._noise_seed = (mode, float(scale)), None if seed is None else int(seed)
-        self._set_noise()
+        """EnvsActing.set_action_noise.  Only the action changes: the records, (c, h), the ring, the
+        windows and the training on every window are as without noise."""
+        EnvsActing.set_action_noise(self, mode, scale, seed)
 
-    def _set_noise(self):
-        nz = an.native(*self._noise, self._envs_seed if self._noise_seed is None else self._noise_seed)
-        nat.check(self._lib.rdl_envs_set_action_noise(self._h, ctypes.byref(nz)), "rdl_envs_set_action_noise")
-
-    @property
-    def action_noise(self) -> dict:
-        """dict(mode, scale, seed): the handle's setting (rdl_envs_action_noise)"""
-        nz = nat.RdActionNoise()
-        nat.check(self._lib.rdl_envs_action_noise(self._h, ctypes.byref(nz)), "rdl_envs_action_noise")
-        return dict(mode=an.MODE_NAMES[nz.mode], scale=float(nz.scale), seed=int(nz.seed))
-
-    @property
-    def actions(self):
-        """[accum_steps, n, 2] f32, the trainer's own and rewritten by every envs call of either actor:
-        the action that stepped env i at the call's k-th step (the acting mean when the noise is off);
-        rows past a shorter call's ``steps`` keep their old values.  None unless attach_envs(...,
-        actions=True) asked for it."""
-        return self._actions
-
-    # -- DAgger's beta-mixture in the student-stepped envs calls ----------------------------------
     def set_teacher_share(self, beta: float, seed: int | None = None):
-        """The teacher's share beta in [0, 1] of the env steps in act_envs / rollout_envs / step_envs
-        ("student") from the next call on (rdl_envs_set_teacher_share; "teacher" calls ignore it): per env
-        and step a coin, a function of (seed, env_base + i, episode, step) alone -- Philox, word 3 of the
-        counter = 0x80000000 | step, u < beta -- hands the teacher's mean to env.step instead of the
-        student's and writes 0 to the record's stepped_with; everything else of the step ((c, h), the
-        ring, the windows) and the training is the student call's.  ``seed``: the coins' key (default:
-        the envs' seed, whatever attach_envs sets it to).  beta = 0 (the default) is the plain student
-        call.  A captured call keeps the beta it was captured with."""
-        beta = float(beta)
-        if not 0.0 <= beta <= 1.0:
-            raise ValueError(f"beta must be in [0, 1], got {beta}")
-        self._coin_seed = None if seed is None else int(seed)
-        self._set_share(beta)
-
-    def _set_share(self, beta: float):
-        seed = self._envs_seed if self._coin_seed is None else self._coin_seed
-        nat.check(self._lib.rdl_envs_set_teacher_share(self._h, beta, seed % 2 ** 64), "rdl_envs_set_teacher_share")
-
-    @property
-    def teacher_share(self) -> float:
-        return float(self._lib.rdl_envs_teacher_share(self._h))
+        """EnvsActing.set_teacher_share.  A step the teacher's coin took writes 0 to the record's
+        stepped_with; (c, h), the ring and the windows are the student call's."""
+        EnvsActing.set_teacher_share(self, beta, seed)
 
     def reset_envs(self):
         """Every env back to its episode 0; clock, carried reward, query state and history to 0."""

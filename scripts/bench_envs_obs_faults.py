@@ -11,7 +11,8 @@ Timing.  Cases: the MLP student at 4,096 envs, K = 50, f32 and bf16; the LSTM st
 
 The driver (no GPU work of its own) runs ``--rounds`` rounds, each of three child processes in turn:
 one on the parent checkout (``--parent DIR``: a tree of the parent commit with its library built;
-variant off, which uses nothing but step_envs), one on this checkout that likewise never touches the
+variant off, which uses nothing but step_envs -- or ``--parent-variants off,on`` for a parent that has the
+faults already, which it then runs as this checkout's third process does), one on this checkout that likewise never touches the
 faults (off: the default), and one on this checkout with off and on, one step of each in turn per
 repetition -- parent, here, here, parent, here, here, ...  Each step is timed with device events.
 Reported per case and variant: median, quartiles and interquartile range over the pooled repetitions of
@@ -65,6 +66,7 @@ def child(a):
     from reacherdistilation_amd.student_mlp import StudentMlpConfig, StudentMlpTrainer
     variants = a.variants.split(",")
     here = variants != ["off"]   # a checkout from before the faults has nothing to select
+    own = os.path.abspath(a.root) == HERE_ROOT   # the cases beyond the comparison run on this checkout only
 
     def run(trainer, info):
         def select(v):
@@ -99,7 +101,7 @@ def child(a):
     st.attach_envs(n, seed=0, accum_steps=K)
     out.append(run(st, dict(student="lstm", n_envs=n, dtype="f32", env_steps_per_opt_step=K, windows_per_opt_step=B)))
     res = dict(device=torch.cuda.get_device_name(0), results=out)
-    if here:
+    if here and own:
         out.append(mlp(a.big_envs, "f32"))
         sm = StudentMlpTrainer(device=DEV)
         sm.set_teacher(tr.teacher)
@@ -151,6 +153,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", nargs="?", default="driver", choices=["driver", "child", "experiment"])
     ap.add_argument("--parent", help="a tree of the parent commit with its library built")
+    ap.add_argument("--parent-variants", default="off", help="off,on: the parent has the faults too")
     ap.add_argument("--root", default=HERE_ROOT)
     ap.add_argument("--variants", default="off,on")
     ap.add_argument("--envs", type=int, default=4096)
@@ -175,7 +178,7 @@ if __name__ == "__main__":
     common =["--envs", str(a.envs), "--big-envs", str(a.big_envs), "--reps", str(a.reps), "--warmup", str(a.warmup)]
     pooled, rounds, device, ev = {}, [], None, {"plain": [], "faulty": []}
     for r in range(a.rounds):   # parent, here (default), here (off and on in turn), parent, ...
-        for label, root, variants in (("parent", os.path.abspath(a.parent), "off"), ("here_default", HERE_ROOT, "off"),
+        for label, root, variants in (("parent", os.path.abspath(a.parent), a.parent_variants), ("here_default", HERE_ROOT, "off"),
                                       ("here", HERE_ROOT, "off,on")):
             got = spawn("child", root, os.path.join(a.tmp, f"faults_{label}_{r}.json"), common + ["--variants", variants])
             device = got["device"]
@@ -195,6 +198,8 @@ if __name__ == "__main__":
         if "parent_off" in med:
             row["median_here_default_off_over_parent_off"] = med["here_default_off"] / med["parent_off"]
             row["median_here_off_over_parent_off"] = med["here_off"] / med["parent_off"]
+        if "parent_on" in med:
+            row["median_here_on_over_parent_on"] = med["here_on"] / med["parent_on"]
         row["median_here_on_over_here_off"] = med["here_on"] / med["here_off"]
         results.append(row)
     res = dict(device=device,
@@ -203,6 +208,7 @@ if __name__ == "__main__":
                       "never touches the faults (off), one on this checkout (off, on: one step of each in turn per "
                       "repetition); repetitions pooled over the rounds; quartiles by statistics.quantiles",
                variants=dict(parent_off="the parent commit, step_envs as it was",
+                             parent_on="the parent commit under --parent-variants off,on: as here_on",
                              here_default_off="this checkout, step_envs alone: the faults never set",
                              here_off="this checkout, faults \"none\" (set back from \"missing\")",
                              here_on="this checkout, set_obs_faults(\"missing\", 0.5), no noise, beta = 0"),

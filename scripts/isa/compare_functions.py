@@ -1,6 +1,7 @@
 """Compare the instruction text of kernel functions between two builds of libreacher.so.
 
     python scripts/isa/compare_functions.py OLD.so NEW.so REGEX [REGEX ...] [--out report.txt]
+                                            [--rename REGEX=REPL ...]
 
 Both libraries' gfx950 code objects are extracted (llvm-objdump --offloading, on copies in a
 temporary folder) and disassembled; every function whose DEMANGLED name matches one of the regular
@@ -10,6 +11,8 @@ relative to the function's start, so a function that only moved inside the objec
 Functions are paired by demangled name.  A template that gained trailing defaulted parameters: where
 NEW has no function of OLD's name, its partner is the one function of NEW whose template arguments
 are OLD's followed by further ones none of which is `true` (the defaults of a new switch: false, a type).
+A template that lost a parameter: --rename REGEX=REPL (re.sub) rewrites OLD's names before the pairing;
+the report names both.
 Exit status 1 if a paired function differs or a function of OLD has no partner.
 """
 from __future__ import annotations
@@ -81,7 +84,9 @@ def main() -> int:
     ap.add_argument("new")
     ap.add_argument("patterns", nargs="+")
     ap.add_argument("--out")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
     a = ap.parse_args()
+    renames = [r.split("=", 1) for r in a.rename]
     tmp = tempfile.mkdtemp(prefix="rd_isa_")
     try:
         sides = []
@@ -96,7 +101,10 @@ def main() -> int:
     lines, bad = [], 0
     paired = set()
     for name in sorted(old):
-        partner = partner_of(name, new)
+        renamed = name
+        for pat, repl in renames:
+            renamed = re.sub(pat, repl, renamed)
+        partner = partner_of(renamed, new)
         if partner is None:
             lines.append(f"MISSING   {name}")
             bad += 1
